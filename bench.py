@@ -6,6 +6,8 @@ d_head 64, 8k tokens per GPU => 64k total at ring_size 8).  Weak scaling:
 per-GPU sequence shard is fixed as N grows.
 
 Single process:   python bench.py --gpus 1 --steps 20 --warmup 5
+  --dump-outputs DIR  also writes the last timed step's out/dq/dk/dv as .npy
+  --full              reserved for measurements beyond the headline figure
 Multi-GPU (driver): torchrun --nproc-per-node N bench.py --gpus N ...
   (one rank per GPU over RCCL; reads RANK/LOCAL_RANK/WORLD_SIZE/MASTER_*)
 
@@ -23,6 +25,30 @@ import sys
 import time
 
 import torch
+
+
+# --dump-outputs writes at most this many bytes over all arrays; an array
+# over its share is cut to a fixed, seeded sample of its flattened elements
+DUMP_BUDGET_BYTES = 32 * 1000 * 1000
+
+
+def dump_outputs(path, outputs):
+    """Write {name: tensor} as path/<name>.npy (float32).  The inputs are
+    seeded, so two builds given the same arguments can be compared array by
+    array.  Sampled arrays keep their element order (sorted flat indices)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // 4 // max(len(outputs), 1)   # fp32 elements
+    for i, (name, t) in enumerate(sorted(outputs.items())):
+        flat = t.detach().reshape(-1)
+        if flat.numel() > share:
+            rng = np.random.default_rng(20240 + i)
+            idx = np.sort(rng.integers(0, flat.numel(), size=share))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            arr = flat.float().cpu().numpy()
+        else:
+            arr = flat.float().cpu().numpy().reshape(tuple(t.shape))
+        np.save(os.path.join(path, name + ".npy"), arr)
 
 
 def main():
@@ -49,6 +75,14 @@ def main():
                     help="BASELINE.json config preset: 2=non-causal ring 64k-class, "
                          "3=causal striped 256k-class, 4=GQA 32q/4kv zig-zag "
                          "causal 1M-class, 5=tree-decode step 128k KV")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed "
+                         "step returned (out, and dq/dk/dv unless forward-"
+                         "only) as DIR/<name>.npy in float32")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline "
+                         "figure (there are none yet: a plain run already "
+                         "does only set-up, warm-up and the timed steps)")
     args = ap.parse_args()
 
     # BASELINE.json config presets (per-GPU shards of the 8-GPU configs, so
@@ -105,10 +139,10 @@ def main():
             c5 = quantize_kv_cache(k5, v5)
 
             def step():
-                tree_attn_decode_fp8(q5, *c5)
+                return {"out": tree_attn_decode_fp8(q5, *c5)}
         else:
             def step():
-                tree_attn_decode(q5, k5, v5, shard_kv_seq=False)
+                return {"out": tree_attn_decode(q5, k5, v5, shard_kv_seq=False)}
     elif args.config == 4:
         # zig-zag causal GQA + fused rotary (per-GPU slice of the 1M config)
         from ring_attention_amd.zigzag import zig_zag_attn
@@ -130,9 +164,12 @@ def main():
             out = zig_zag_attn(qr.permute(0, 2, 1, 3), kr.permute(0, 2, 1, 3),
                                v.permute(0, 2, 1, 3), causal=True,
                                q_chunk_starts=starts)
+            res = {"out": out}
             if not args.fwd_only:
                 out.backward(out.detach())
+                res.update(dq=q.grad, dk=k.grad, dv=v.grad)
                 q.grad = None; k.grad = None; v.grad = None
+            return res
     elif getattr(args, "fp8", False) and on_gpu:
         # MX-FP8 serving forward: quantization is per-prefill (outside the
         # step, like a KV-cache write); the step is the fused e4m3 forward
@@ -145,7 +182,9 @@ def main():
         fp8_scale = d ** -0.5
 
         def step():
-            flash_attn_fp8_quantized(*fp8_args, fp8_scale, causal=args.causal)
+            out, lse = flash_attn_fp8_quantized(*fp8_args, fp8_scale,
+                                                causal=args.causal)
+            return {"out": out, "lse": lse}
     else:
         q = torch.randn(b, n, h, d, device=device, dtype=dtype, requires_grad=True)
         k = torch.randn(b, n, hk, d, device=device, dtype=dtype, requires_grad=True)
@@ -156,9 +195,12 @@ def main():
                           striped_ring_attn=args.striped, ring_size=world,
                           bucket_size=min(n, 1024),
                           softclamp_qk_sim=args.softclamp)
+            res = {"out": out}
             if not args.fwd_only:
                 out.backward(out.detach())  # fwd + full bwd (dq, dk, dv incl. ring)
+                res.update(dq=q.grad, dk=k.grad, dv=v.grad)
                 q.grad = None; k.grad = None; v.grad = None
+            return res
 
     for _ in range(args.warmup):
         step()
@@ -177,7 +219,7 @@ def main():
             torch.cuda.synchronize()
             g_ = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g_):
-                step()
+                graph_outputs = step()   # static tensors every replay refills
             g_.replay()
             torch.cuda.synchronize()
             graph = g_
@@ -189,8 +231,12 @@ def main():
     if on_gpu:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        graph.replay() if graph is not None else step()
+        if graph is not None:
+            graph.replay()
+        else:
+            last = step()
     if distributed:
         torch.distributed.barrier()
     if on_gpu:
@@ -205,6 +251,10 @@ def main():
         elapsed = elapsed_d.cpu()
     secs = float(elapsed.item())
     ms_per_step = secs / args.steps * 1e3
+
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs,
+                     (graph_outputs if graph is not None else last) or {})
 
     n_total = n * world
     fwd_flops_per_gpu = 4.0 * b * n * n_total * d * h

@@ -19,8 +19,11 @@ def test_torchrun_gloo_bench_smoke():
            "--master-port", "29517",
            os.path.join(repo, "bench.py"), "--gpus", "4",
            "--steps", "2", "--warmup", "1"]
+    # a CPU/gloo rehearsal wherever it runs: hide any GPUs from the ranks
+    # (4 ranks on a box with fewer GPUs have no device to bind to)
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=280,
-                       cwd=repo)
+                       cwd=repo, env=env)
     assert r.returncode == 0, f"torchrun failed:\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}"
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     rec = json.loads(line)
