@@ -30,6 +30,10 @@
 //   dq: fp32 (B, Nq, H, D)   — plain accumulate (+=) across hops
 //   dk: fp32 (B, HK, Nk, D)  — plain writes (one WG owns each row)
 //   dv: fp32 (B, HK, D, Nk)  — transposed scratch, coalesced from dv^T regs
+// Single-pass launches may instead pass bf16 dq_bf (B, Nq, H, D) and
+// dk_bf/dv_bf (B, Nk, HK, D): the epilogues round and store the final
+// gradients themselves; attn_bwd_finalize_kernel does the same in one launch
+// for the fp32 scratch of the accumulating modes.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -420,6 +424,23 @@ void attn_bwd_dq_kernel(BwdParams p) { // cap 256 VGPR, stop the 220 B/thread
     }
 
     if (!row_valid) return;
+    if (P.dq_bf) {
+        // fused epilogue (single-pass only, enforced by the binding): this
+        // lane is the unique writer of its row, so round the finished fp32
+        // value (RNE) and store bf16 at its final address — regs 4g..4g+3
+        // are 4 consecutive d, one 8-byte store each
+        __bf16* dqb = (__bf16*)P.dq_bf + ((long)b * P.nq + i) * P.h * D + (long)h * D;
+        #pragma unroll
+        for (int db = 0; db < DBLK; ++db)
+            #pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                f32x4 v4 = {dq_acc[db][4 * g], dq_acc[db][4 * g + 1],
+                            dq_acc[db][4 * g + 2], dq_acc[db][4 * g + 3]};
+                *(bf16x4*)(dqb + db * 32 + 8 * g + 4 * lhi) =
+                    __builtin_convertvector(v4, bf16x4);
+            }
+        return;
+    }
     // epilogue: dq (B, Nq, H, D) fp32; unique writer per row unless the kv
     // walk is split across grid.z (then fp32 atomics, contention = split)
     float* dqp = P.dq + ((long)b * P.nq + i) * P.h * D + (long)h * D;
@@ -807,8 +828,65 @@ void attn_bwd_dkv_kernel(BwdParams p) {
         }
     }
 
-    // write dk (B,HK,Nk,D) and dv^T (B,HK,D,Nk)
-    if (col_valid) {
+    if (P.dk_bf) {
+        // fused epilogue (single-pass only, enforced by the binding): this
+        // WG is the unique writer of its 256 kv rows, so round the finished
+        // fp32 values (RNE) and store bf16 in the caller's (B,Nk,HK,D)
+        // layout.  dk lanes own a d COLUMN (2-byte direct stores), so the
+        // tile is transposed through the Q/dO LDS images, which are dead
+        // once every wave has left the last q tile: [256][D] bf16 dk, then
+        // [256][D] bf16 dv (2 x 32 KB at d64 of the 65 KB allocated), same
+        // 16-byte-chunk XOR swizzle as the staged images.  Each wave writes
+        // and reads back only its own 32 rows; rows leave as 16-byte stores.
+        // (dv could leave straight from registers, 8 B per lane: measured
+        // equal at the headline shape — docs/KERNELS.md §2 — so both
+        // tensors share the one staged store loop.)
+        constexpr int ECH = D / 8;
+        __bf16* stg_dk = (__bf16*)&lds;
+        __bf16* stg_dv = stg_dk + KVROWS_WG * D;
+        static_assert(sizeof(DkvLds<D, QT>) >= 2 * KVROWS_WG * D * sizeof(__bf16));
+        const int wrow0 = wid * KVROWS_WAVE;
+        const long orow_stride = (long)P.hk * D;
+        __bf16* dkb = (__bf16*)P.dk_bf + ((long)b * P.nk) * orow_stride + (long)hkh * D;
+        __bf16* dvb = (__bf16*)P.dv_bf + ((long)b * P.nk) * orow_stride + (long)hkh * D;
+        __syncthreads();                       // last tile's readers are done
+        #pragma unroll
+        for (int db = 0; db < DBLK; ++db)
+            #pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                int row = wrow0 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
+                int d = db * 32 + l31;
+                stg_dk[row * D + bswz<ECH>(row, d / 8) * 8 + (d & 7)] = (__bf16)dk_acc[db][r];
+            }
+        {
+            // dv^T regs 4g..4g+3 are 4 consecutive d of this lane's kv row
+            const int row = wrow0 + l31;
+            #pragma unroll
+            for (int db = 0; db < DBLK; ++db)
+                #pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    f32x4 v4 = {dv_acc[db][4 * g], dv_acc[db][4 * g + 1],
+                                dv_acc[db][4 * g + 2], dv_acc[db][4 * g + 3]};
+                    *(bf16x4*)(stg_dv + row * D + bswz<ECH>(row, db * 4 + g) * 8 + 4 * lhi) =
+                        __builtin_convertvector(v4, bf16x4);
+                }
+        }
+        __syncthreads();
+        #pragma unroll
+        for (int c = lane; c < KVROWS_WAVE * ECH; c += 64) {
+            int row = wrow0 + c / ECH, ch = c % ECH;
+            long kvrow = j0_wg + row;
+            if (kvrow <= jmax) {
+                int so = row * D + bswz<ECH>(row, ch) * 8;
+                *(uint4*)(dkb + kvrow * orow_stride + ch * 8) = *(const uint4*)(stg_dk + so);
+                *(uint4*)(dvb + kvrow * orow_stride + ch * 8) = *(const uint4*)(stg_dv + so);
+            }
+        }
+    } else {
+        // write dk (B,HK,Nk,D) and dv^T (B,HK,D,Nk).  dk: the lane owns a d
+        // COLUMN of all 32 kv rows of its wave, so only the row guard
+        // applies (gating on the lane's own kv row left columns of a
+        // partially valid wave unwritten when Nk % 32 != 0)
         float* dkb = P.dk + (((long)b * P.hk + hkh) * P.nk) * D;
         #pragma unroll
         for (int db = 0; db < DBLK; ++db)
@@ -824,6 +902,7 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                 }
             }
         float* dvb = P.dv + (((long)b * P.hk + hkh) * D) * P.nk;
+        if (col_valid)
         #pragma unroll
         for (int db = 0; db < DBLK; ++db)
             #pragma unroll
@@ -974,6 +1053,97 @@ void launch_attn_delta(const DeltaParams& p, int head_dim, hipStream_t stream) {
     } else {
         __builtin_trap();
     }
+}
+
+// ---------------------------------------------------------------------------
+// finalize: ONE launch turning the fp32-accumulated scratch gradients into
+// bf16 gradients in the caller's layout (replaces two permute-copies and
+// three casts wherever fp32 accumulation is genuinely needed: grid.z splits,
+// descriptor units, multi-hop ring, all-gather reduce-scatter).
+//   grid = (ceil(Nk/64), B*HK, 3): z=0 dk, z=1 dv, z=2 dq (grid-stride cast)
+//   dk fp32 (B,HK,Nk,D) -> bf16 (B,Nk,HK,D): rows are contiguous both sides
+//   dv fp32 (B,HK,D,Nk) -> bf16 (B,Nk,HK,D): 64-kv tile transposed in LDS
+//     (reads coalesced along kv, writes 16 B along d); any Nk
+// Memory-bound: 6 B moved per gradient element.
+// ---------------------------------------------------------------------------
+static constexpr int FIN_ROWS = 64;
+
+__device__ __forceinline__ uint4 fin_pack8(const float* s) {
+    f32x4 a = {s[0], s[1], s[2], s[3]}, c = {s[4], s[5], s[6], s[7]};
+    union { bf16x4 h[2]; uint4 u; } o;
+    o.h[0] = __builtin_convertvector(a, bf16x4);
+    o.h[1] = __builtin_convertvector(c, bf16x4);
+    return o.u;
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void attn_bwd_finalize_kernel(BwdFinalizeParams p) {
+    constexpr int CH = D / 8;
+    constexpr int LDW = FIN_ROWS + 1;          // padded kv pitch (floats)
+    __shared__ float tile[D * LDW];
+    const int tid = threadIdx.x;
+    const int which = blockIdx.z;
+
+    if (which == 2) {
+        if (!p.dq) return;
+        const long nblk = (long)gridDim.x * gridDim.y;
+        const long blk = (long)blockIdx.y * gridDim.x + blockIdx.x;
+        const long chunks = p.dq_elems / 8;
+        for (long c = blk * 256 + tid; c < chunks; c += nblk * 256) {
+            float s[8];
+            *(f32x4*)s = *(const f32x4*)(p.dq + c * 8);
+            *(f32x4*)(s + 4) = *(const f32x4*)(p.dq + c * 8 + 4);
+            *(uint4*)((__bf16*)p.dq_bf + c * 8) = fin_pack8(s);
+        }
+        return;
+    }
+    if (!p.dk) return;
+
+    const int bb = blockIdx.y / p.hk;
+    const int hh = blockIdx.y % p.hk;
+    const long n0 = (long)blockIdx.x * FIN_ROWS;
+    const int rows = (int)min((long)FIN_ROWS, p.nk - n0);
+    const long orow_stride = (long)p.hk * D;
+
+    if (which == 0) {
+        const float* src = p.dk + (((long)bb * p.hk + hh) * p.nk + n0) * D;
+        __bf16* dst = (__bf16*)p.dk_bf + ((long)bb * p.nk + n0) * orow_stride + (long)hh * D;
+        for (int c = tid; c < rows * CH; c += 256) {
+            int row = c / CH, ch = c % CH;
+            float s[8];
+            *(f32x4*)s = *(const f32x4*)(src + (long)row * D + ch * 8);
+            *(f32x4*)(s + 4) = *(const f32x4*)(src + (long)row * D + ch * 8 + 4);
+            *(uint4*)(dst + row * orow_stride + ch * 8) = fin_pack8(s);
+        }
+        return;
+    }
+
+    // dv: source rows are d, kv contiguous — scalar loads (any Nk alignment)
+    const float* src = p.dv + (((long)bb * p.hk + hh) * D) * p.nk + n0;
+    for (int c = tid; c < D * FIN_ROWS; c += 256) {
+        int d = c / FIN_ROWS, nn = c % FIN_ROWS;
+        if (nn < rows) tile[d * LDW + nn] = src[(long)d * p.nk + nn];
+    }
+    __syncthreads();
+    __bf16* dst = (__bf16*)p.dv_bf + ((long)bb * p.nk + n0) * orow_stride + (long)hh * D;
+    for (int c = tid; c < rows * CH; c += 256) {
+        int row = c / CH, ch = c % CH;
+        float s[8];
+        #pragma unroll
+        for (int e = 0; e < 8; ++e) s[e] = tile[(ch * 8 + e) * LDW + row];
+        *(uint4*)(dst + row * orow_stride + ch * 8) = fin_pack8(s);
+    }
+}
+
+void launch_attn_bwd_finalize(const BwdFinalizeParams& p, int head_dim, hipStream_t stream) {
+    dim3 block(256);
+    long nx = p.dk ? (p.nk + FIN_ROWS - 1) / FIN_ROWS : 256;
+    int ny = p.dk ? p.b * p.hk : 1;
+    dim3 grid(nx, ny, p.dq ? 3 : 2);
+    if (head_dim == 64) hipLaunchKernelGGL(attn_bwd_finalize_kernel<64>, grid, block, 0, stream, p);
+    else if (head_dim == 128) hipLaunchKernelGGL(attn_bwd_finalize_kernel<128>, grid, block, 0, stream, p);
+    else if (head_dim == 32) hipLaunchKernelGGL(attn_bwd_finalize_kernel<32>, grid, block, 0, stream, p);
+    else __builtin_trap();
 }
 
 }  // namespace ring_attn

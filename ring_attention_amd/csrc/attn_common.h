@@ -15,6 +15,7 @@ typedef __bf16 bf16_t;
 typedef bf16_t bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef bf16_t bf16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 #endif
 
@@ -89,9 +90,17 @@ struct BwdParams {
     const void* kmask;      // uint8 (B, Nk) or nullptr
     const float* lse;       // fp32 (B, H, Nq)
     const float* delta;     // fp32 (B, H, Nq)  rowsum(do*o)
-    float* dq;              // fp32 (B, Nq, H, D)  accumulated via atomics
-    float* dk;              // fp32 (B, Nk, HK, D) accumulated (plain adds per WG)
-    float* dv;              // fp32 (B, Nk, HK, D)
+    float* dq;              // fp32 (B, Nq, H, D)  plain write / += / atomics
+    float* dk;              // fp32 (B, HK, Nk, D) kernel scratch layout
+    float* dv;              // fp32 (B, HK, D, Nk) transposed scratch layout
+    // fused epilogue (single-pass launches only: split <= 1, no desc, no
+    // accumulate — the kernel is then the unique writer of every element).
+    // When set, the epilogue rounds its fp32 accumulator to bf16 (RNE) and
+    // stores it HERE in the caller's final layout; the matching fp32 buffer
+    // above is not touched and may be null.
+    void* dq_bf;            // bf16 (B, Nq, H, D) or null
+    void* dk_bf;            // bf16 (B, Nk, HK, D) or null
+    void* dv_bf;            // bf16 (B, Nk, HK, D) or null
     int b, h, hk, group;
     long nq, nk;
     float scale;
@@ -118,6 +127,23 @@ struct BwdParams {
 
 void launch_attn_bwd_dq(const BwdParams& p, int head_dim, hipStream_t stream);
 void launch_attn_bwd_dkv(const BwdParams& p, int head_dim, hipStream_t stream);
+
+// One-launch finish for the fp32-accumulating backward paths (grid.z splits,
+// descriptor units, multi-hop ring, all-gather reduce-scatter): fp32 scratch
+// layouts -> bf16 gradients in the caller's (B, N, HK, D) layout.
+struct BwdFinalizeParams {
+    const float* dk;        // fp32 (B, HK, Nk, D) or null
+    const float* dv;        // fp32 (B, HK, D, Nk) or null (with dk)
+    const float* dq;        // fp32, dq_elems values (flat cast) or null
+    void* dk_bf;            // bf16 (B, Nk, HK, D)
+    void* dv_bf;            // bf16 (B, Nk, HK, D)
+    void* dq_bf;            // bf16, dq_elems values
+    int b, hk;
+    long nk;
+    long dq_elems;          // multiple of 8
+};
+
+void launch_attn_bwd_finalize(const BwdFinalizeParams& p, int head_dim, hipStream_t stream);
 
 struct DeltaParams {
     const void* dout;       // bf16 (B, N, H, D)

@@ -148,22 +148,59 @@ void attn_bwd(
     at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor dout,
     std::optional<at::Tensor> kmask,
     at::Tensor lse, at::Tensor delta,
-    at::Tensor dq, at::Tensor dk, at::Tensor dv,
+    std::optional<at::Tensor> dq, std::optional<at::Tensor> dk,
+    std::optional<at::Tensor> dv,
     double scale, bool causal, int64_t diag, int64_t q_stride,
     int64_t win, bool has_win,
     bool softclamp, double softclamp_value, bool accumulate, int64_t split,
     int64_t which,     // 0 = both, 1 = dq only, 2 = dk/dv only
     std::optional<at::Tensor> desc_dq,    // int32 (U,3): tile, t_lo, t_hi
     std::optional<at::Tensor> desc_dkv,
-    std::optional<at::Tensor> bias, bool bias_mat) {
+    std::optional<at::Tensor> bias, bool bias_mat,
+    // fused epilogue: final-layout bf16 gradients written by the kernels
+    // themselves (dq (B,Nq,H,D); dk, dv (B,Nk,HK,D)); single-pass only
+    std::optional<at::Tensor> dq_bf, std::optional<at::Tensor> dk_bf,
+    std::optional<at::Tensor> dv_bf) {
     CHECK_BF16_CONTIG(q); CHECK_BF16_CONTIG(k); CHECK_BF16_CONTIG(v); CHECK_BF16_CONTIG(dout);
     CHECK_F32_CONTIG(lse); CHECK_F32_CONTIG(delta);
-    CHECK_F32_CONTIG(dq); CHECK_F32_CONTIG(dk); CHECK_F32_CONTIG(dv);
     const int64_t B = q.size(0), Nq = q.size(1), H = q.size(2), D = q.size(3);
     const int64_t Nk = k.size(1), HK = k.size(2);
     TORCH_CHECK(D == 32 || D == 64 || D == 128, "head dim must be 32/64/128");
-    TORCH_CHECK(dq.numel() == q.numel() && dk.numel() == k.numel() && dv.numel() == v.numel());
     TORCH_CHECK(lse.numel() == B * H * Nq && delta.numel() == B * H * Nq);
+    const bool run_dq = which == 0 || which == 1;
+    const bool run_dkv = which == 0 || which == 2;
+    if (dq_bf || dk_bf || dv_bf) {
+        // the other modes sum in fp32 across workgroups (grid.z splits,
+        // descriptor units) or across hops (accumulate): rounding per
+        // contribution would change the result
+        TORCH_CHECK(split <= 1 && !accumulate && !desc_dq && !desc_dkv,
+                    "bf16 gradient outputs need a single-pass launch "
+                    "(split <= 1, no descriptors, accumulate=false)");
+        TORCH_CHECK(dk_bf.has_value() == dv_bf.has_value(),
+                    "dk_bf and dv_bf go together");
+    }
+    if (dq_bf) {
+        CHECK_BF16_CONTIG((*dq_bf));
+        TORCH_CHECK(dq_bf->sizes() == q.sizes(), "dq_bf must be (B,Nq,H,D)");
+        TORCH_CHECK((uintptr_t)dq_bf->data_ptr() % 8 == 0, "dq_bf must be 8-byte aligned");
+    } else if (run_dq) {
+        TORCH_CHECK(dq.has_value(), "dq launch needs an fp32 dq or a bf16 dq_bf");
+    }
+    if (dk_bf) {
+        CHECK_BF16_CONTIG((*dk_bf)); CHECK_BF16_CONTIG((*dv_bf));
+        TORCH_CHECK(dk_bf->sizes() == k.sizes() && dv_bf->sizes() == v.sizes(),
+                    "dk_bf/dv_bf must be (B,Nk,HK,D)");
+        // rows leave the kernel as 16-byte stores
+        TORCH_CHECK((uintptr_t)dk_bf->data_ptr() % 16 == 0
+                    && (uintptr_t)dv_bf->data_ptr() % 16 == 0,
+                    "dk_bf/dv_bf must be 16-byte aligned");
+    } else if (run_dkv) {
+        TORCH_CHECK(dk.has_value() && dv.has_value(),
+                    "dk/dv launch needs fp32 dk, dv or bf16 dk_bf, dv_bf");
+    }
+    if (dq) { CHECK_F32_CONTIG((*dq)); TORCH_CHECK(dq->numel() == q.numel()); }
+    if (dk) { CHECK_F32_CONTIG((*dk)); TORCH_CHECK(dk->numel() == k.numel()); }
+    if (dv) { CHECK_F32_CONTIG((*dv)); TORCH_CHECK(dv->numel() == v.numel()); }
 
     BwdParams p{};
     p.q = q.data_ptr(); p.k = k.data_ptr(); p.v = v.data_ptr(); p.dout = dout.data_ptr();
@@ -173,7 +210,12 @@ void attn_bwd(
         p.kmask = kmask->data_ptr();
     }
     p.lse = lse.data_ptr<float>(); p.delta = delta.data_ptr<float>();
-    p.dq = dq.data_ptr<float>(); p.dk = dk.data_ptr<float>(); p.dv = dv.data_ptr<float>();
+    p.dq = dq ? dq->data_ptr<float>() : nullptr;
+    p.dk = dk ? dk->data_ptr<float>() : nullptr;
+    p.dv = dv ? dv->data_ptr<float>() : nullptr;
+    p.dq_bf = dq_bf ? dq_bf->data_ptr() : nullptr;
+    p.dk_bf = dk_bf ? dk_bf->data_ptr() : nullptr;
+    p.dv_bf = dv_bf ? dv_bf->data_ptr() : nullptr;
     p.b = (int)B; p.h = (int)H; p.hk = (int)HK; p.group = (int)(H / HK);
     p.nq = Nq; p.nk = Nk;
     p.scale = (float)scale;
@@ -206,14 +248,14 @@ void attn_bwd(
             p.n_units = dsc->size(0);
         }
     };
-    if (which == 0 || which == 1) {
+    if (run_dq) {
         const long Tq = (Nq + 255) / 256;
         set_desc(desc_dq);
         p.paired = (!p.desc && pair_ok && ((Tq + 1) / 2) * B * H * z >= 256)
                        ? (int)Tq : 0;
         launch_attn_bwd_dq(p, (int)D, at::hip::getCurrentHIPStream());
     }
-    if (which == 0 || which == 2) {
+    if (run_dkv) {
         const long Tk = (Nk + 255) / 256;
         set_desc(desc_dkv);
         p.paired = (!p.desc && pair_ok && ((Tk + 1) / 2) * B * HK * z >= 256)
@@ -221,6 +263,47 @@ void attn_bwd(
         launch_attn_bwd_dkv(p, (int)D, at::hip::getCurrentHIPStream());
     }
     TORCH_CHECK(hipGetLastError() == hipSuccess, "attn_bwd launch failed");
+}
+
+std::vector<std::optional<at::Tensor>> attn_bwd_finalize(
+    std::optional<at::Tensor> dk, std::optional<at::Tensor> dv,
+    std::optional<at::Tensor> dq) {
+    // dk fp32 (B,HK,Nk,D), dv fp32 (B,HK,D,Nk) -> bf16 (B,Nk,HK,D) each;
+    // dq fp32 (any shape, last dim D) -> bf16 same shape.  One launch.
+    // Returns (dq_bf, dk_bf, dv_bf); absent inputs give None.
+    TORCH_CHECK(dk.has_value() == dv.has_value(), "dk and dv go together");
+    TORCH_CHECK(dk || dq, "nothing to finalize");
+    BwdFinalizeParams p{};
+    std::optional<at::Tensor> dq_bf, dk_bf, dv_bf;
+    int64_t D = 0;
+    if (dk) {
+        CHECK_F32_CONTIG((*dk)); CHECK_F32_CONTIG((*dv));
+        TORCH_CHECK(dk->dim() == 4 && dv->dim() == 4, "dk (B,HK,Nk,D), dv (B,HK,D,Nk)");
+        const int64_t B = dk->size(0), HK = dk->size(1), Nk = dk->size(2);
+        D = dk->size(3);
+        TORCH_CHECK(dv->size(0) == B && dv->size(1) == HK && dv->size(2) == D
+                    && dv->size(3) == Nk, "dv must be (B,HK,D,Nk)");
+        TORCH_CHECK((uintptr_t)dk->data_ptr() % 16 == 0, "dk must be 16-byte aligned");
+        dk_bf = at::empty({B, Nk, HK, D}, dk->options().dtype(at::kBFloat16));
+        dv_bf = at::empty({B, Nk, HK, D}, dk->options().dtype(at::kBFloat16));
+        p.dk = dk->data_ptr<float>(); p.dv = dv->data_ptr<float>();
+        p.dk_bf = dk_bf->data_ptr(); p.dv_bf = dv_bf->data_ptr();
+        p.b = (int)B; p.hk = (int)HK; p.nk = Nk;
+    }
+    if (dq) {
+        CHECK_F32_CONTIG((*dq));
+        TORCH_CHECK(dq->dim() >= 1 && (D == 0 || dq->size(-1) == D),
+                    "dq head dim must match dk");
+        if (D == 0) D = dq->size(-1);
+        TORCH_CHECK((uintptr_t)dq->data_ptr() % 16 == 0, "dq must be 16-byte aligned");
+        dq_bf = at::empty_like(*dq, dq->options().dtype(at::kBFloat16));
+        p.dq = dq->data_ptr<float>(); p.dq_bf = dq_bf->data_ptr();
+        p.dq_elems = dq->numel();
+    }
+    TORCH_CHECK(D == 32 || D == 64 || D == 128, "head dim must be 32/64/128");
+    launch_attn_bwd_finalize(p, (int)D, at::hip::getCurrentHIPStream());
+    TORCH_CHECK(hipGetLastError() == hipSuccess, "attn_bwd_finalize launch failed");
+    return {dq_bf, dk_bf, dv_bf};
 }
 
 at::Tensor rotary_apply(at::Tensor x, at::Tensor cos_t, at::Tensor sin_t, double sin_sign) {
@@ -406,7 +489,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::arg("has_win"), py::arg("softclamp"), py::arg("softclamp_value"),
             py::arg("accumulate"), py::arg("split"), py::arg("which"),
             py::arg("desc_dq"), py::arg("desc_dkv"),
-            py::arg("bias") = std::nullopt, py::arg("bias_mat") = false);
+            py::arg("bias") = std::nullopt, py::arg("bias_mat") = false,
+            py::arg("dq_bf") = std::nullopt, py::arg("dk_bf") = std::nullopt,
+            py::arg("dv_bf") = std::nullopt);
+    mod.def("attn_bwd_finalize", &ring_attn::attn_bwd_finalize,
+            "fp32 scratch gradients -> final-layout bf16 (one launch)",
+            py::arg("dk"), py::arg("dv"), py::arg("dq") = std::nullopt);
     mod.def("decode_partial", &ring_attn::decode_partial, "CDNA4 single-query decode partial",
             py::arg("q"), py::arg("k"), py::arg("v"), py::arg("sm_scale") = -1.0,
             py::arg("chunks") = 0);

@@ -26,7 +26,17 @@ chunk takes a share of its WG's own valid range) for 256-512-WG grids;
 under-filled GQA dkv grids instead use host-built constant-work descriptor
 units (_walk_descriptors) with fp32-atomic accumulation.  Env overrides:
 RING_ATTN_NO_PAIR, RING_ATTN_NO_DESC, RING_ATTN_KV_SPLIT,
-RING_ATTN_SPLIT_DQ/DKV, RING_ATTN_FORCE_STRATEGY, RING_ATTN_AG_BUDGET.
+RING_ATTN_SPLIT_DQ/DKV, RING_ATTN_FORCE_STRATEGY, RING_ATTN_AG_BUDGET,
+RING_ATTN_NO_FUSED_EPILOGUE.
+
+Gradient epilogue (bf16 inputs): single-pass backward launches (one hop,
+split 1, no descriptors, no accumulation) have the dq/dkv kernels round and
+store bf16 gradients straight into the caller's (b, n, h, d) layout; where
+fp32 accumulation is genuinely needed (grid.z splits, descriptor units,
+multi-hop ring, all-gather reduce-scatter) ONE attn_bwd_finalize launch
+turns the fp32 scratch into the bf16 gradients.  RING_ATTN_NO_FUSED_EPILOGUE=1
+forces the torch permute/contiguous/cast chain instead (A/B runs; also the
+path for non-bf16 inputs).
 
 Capability parity with the reference's ring_flash_attn_cuda
 (/root/reference/ring_attention_pytorch/ring_flash_attention_cuda.py:40-371)
@@ -241,12 +251,36 @@ def _pad_head_dim(q, k, v):
     return F.pad(q, (0, kd - d)), F.pad(k, (0, kd - d)), F.pad(v, (0, kd - d))
 
 
+def _fused_epilogue(in_dtype) -> bool:
+    """bf16 gradients come from the kernels' own epilogue / the finalize
+    kernel (see module docstring); other dtypes keep the torch chain."""
+    return (in_dtype == torch.bfloat16
+            and not os.environ.get("RING_ATTN_NO_FUSED_EPILOGUE"))
+
+
+def _finish_grads(ext, fused, in_dtype, dq, dk_n, dv_n):
+    """fp32 scratch gradients (dq (b,n,h,d), dk (b,hk,nk,d), dv (b,hk,d,nk))
+    -> (dq, dk, dv) in the caller's dtype and (b, n, h, d) layout.  ``dq``
+    may already be the final bf16 tensor (direct epilogue); then only dk/dv
+    are converted."""
+    if fused:
+        dq_bf, dk, dv = ext.attn_bwd_finalize(
+            dk_n, dv_n, dq if dq.dtype == torch.float32 else None)
+        return (dq_bf if dq_bf is not None else dq), dk, dv
+    dk = dk_n.permute(0, 2, 1, 3).contiguous()
+    dv = dv_n.permute(0, 3, 1, 2).contiguous()
+    return dq.to(in_dtype), dk.to(in_dtype), dv.to(in_dtype)
+
+
 class RingFlashAttentionHIPFunction(Function):
     @staticmethod
     def forward(ctx, q, k, v, mask, causal, bucket_size, ring_reduce, striped,
                 max_lookback_seq_len, ring_size, softclamp_qk_sim, softclamp_value,
                 sm_scale=None):
         assert q.is_cuda, "HIP path requires GPU tensors"
+        # backward ignores the lse gradient: do not have autograd fill a
+        # zero tensor for it (or for an unused out) on every step
+        ctx.set_materialize_grads(False)
         b, n, h, d = q.shape
         hk = k.shape[2]
         in_dtype = q.dtype
@@ -386,6 +420,18 @@ class RingFlashAttentionHIPFunction(Function):
     @staticmethod
     def backward(ctx, do, _dlse):
         qb, kb, vb, out, lse, mask_u8 = ctx.saved_tensors
+        if do is None and not ctx.params[6]:
+            # only lse was consumed downstream; its gradient is not
+            # propagated (as before), so q/k/v get exact zeros.  Local runs
+            # only: a ring backward must still enter every collective its
+            # peers enter, so there a zero dO takes the normal path below.
+            in_dtype = ctx.params[8]
+            return (torch.zeros_like(qb, dtype=in_dtype),
+                    torch.zeros_like(kb, dtype=in_dtype),
+                    torch.zeros_like(vb, dtype=in_dtype),
+                    None, None, None, None, None, None, None, None, None, None)
+        if do is None:
+            do = torch.zeros_like(out)
         mask_u8 = mask_u8 if mask_u8.numel() else None
         (causal, striped, lookback, hops, softclamp_qk_sim, softclamp_value,
          use_ring, ring_size, in_dtype, strategy) = ctx.params
@@ -401,6 +447,8 @@ class RingFlashAttentionHIPFunction(Function):
         dob = do.to(torch.bfloat16).contiguous()
         # delta = rowsum(do * o) in fp32: (b, h, n), fused HIP kernel
         delta = ext.attn_delta(dob, out)
+
+        fused = _fused_epilogue(in_dtype)
 
         def _alloc_dq(zeroed):
             fac = torch.zeros if zeroed else torch.empty
@@ -435,18 +483,25 @@ class RingFlashAttentionHIPFunction(Function):
                                          b * hk, qb.device)
             if ddkv is not None:
                 split_dkv = 1
-            dq = _alloc_dq(zeroed=split_dq > 1 or ddq is not None)
+            # dq never leaves this rank: unsplit, the kernel emits it final
+            dq_direct = fused and split_dq == 1 and ddq is None
+            if dq_direct:
+                dq = torch.empty_like(qb)
+            else:
+                dq = _alloc_dq(zeroed=split_dq > 1 or ddq is not None)
             fac = torch.zeros if (split_dkv > 1 or ddkv is not None) else torch.empty
             dk_full = fac(b, hk, n_total, d, device=qb.device, dtype=torch.float32)
             dv_full = fac(b, hk, d, n_total, device=qb.device, dtype=torch.float32)
             ext.attn_bwd(qb, k_full, v_full, dob, m_full, lse, delta,
-                         dq, dk_full, dv_full, scale, causal, diag, q_stride,
+                         None if dq_direct else dq, dk_full, dv_full,
+                         scale, causal, diag, q_stride,
                          lookback if lookback is not None else 0,
                          lookback is not None,
                          softclamp_qk_sim, softclamp_value, False, split_dq, 1,
-                         ddq, None)
+                         ddq, None, dq_bf=dq if dq_direct else None)
             ext.attn_bwd(qb, k_full, v_full, dob, m_full, lse, delta,
-                         dq, dk_full, dv_full, scale, causal, diag, q_stride,
+                         None if dq_direct else dq, dk_full, dv_full,
+                         scale, causal, diag, q_stride,
                          lookback if lookback is not None else 0,
                          lookback is not None,
                          softclamp_qk_sim, softclamp_value, False, split_dkv, 2,
@@ -457,9 +512,10 @@ class RingFlashAttentionHIPFunction(Function):
             packed = torch.cat((dk_chunks.reshape(R, -1), dv_chunks.reshape(R, -1)), dim=1)
             own = reduce_scatter_chunks(packed, group=pg)
             half = own.numel() // 2
-            dk_home = own[:half].view(b, hk, n, d).permute(0, 2, 1, 3).contiguous()
-            dv_home = own[half:].view(b, hk, d, n).permute(0, 3, 1, 2).contiguous()
-            return (dq.to(in_dtype), dk_home.to(in_dtype), dv_home.to(in_dtype),
+            dq, dk_home, dv_home = _finish_grads(
+                ext, fused, in_dtype, dq,
+                own[:half].view(b, hk, n, d), own[half:].view(b, hk, d, n))
+            return (dq, dk_home, dv_home,
                     None, None, None, None, None, None, None, None, None, None)
         # independent grid.z splits: dq's grid is (q-tiles x b*h), dkv's is
         # (kv-tiles x b*hk) — GQA shrinks the latter (e.g. hk=2 -> 64 WGs)
@@ -497,7 +553,13 @@ class RingFlashAttentionHIPFunction(Function):
         first_active = next(i for i, p_ in enumerate(plan) if not p_[0])
         # atomics (grid.z split or descriptor units) need a zeroed base
         dq_zeroed = plan[first_active][3] > 1 or plan[first_active][5] is not None
-        dq = _alloc_dq(zeroed=dq_zeroed)
+        # single-pass launches (one local hop, unsplit, no descriptor units):
+        # the kernels are the unique writers and emit final bf16 gradients
+        single = fused and topo.ring_size == 1 and hops == 1
+        dq_direct = single and not dq_zeroed
+        dkv_direct = (single and plan[0][4] == 1 and plan[0][6] is None)
+        dq = torch.empty_like(qb) if dq_direct else _alloc_dq(zeroed=dq_zeroed)
+        dk_home = dv_home = None
 
         ring_tensors = (kb, vb) if mask_u8 is None else (kb, vb, mask_u8)
         acc = RingAccumulator(topo)
@@ -511,33 +573,45 @@ class RingFlashAttentionHIPFunction(Function):
             # layout-agnostic, so only ONE final permute happens at home.
             # The kernels overwrite every element at split 1, so only the
             # atomic (split/descriptor) and skip (circulated) cases zero-init.
-            fac = (torch.zeros if (skip or split_dkv > 1 or ddkv is not None)
-                   else torch.empty)
-            contrib = fac(2, b * hk * n * d, device=qb.device,
-                          dtype=torch.float32)
-            if not skip:
+            contrib = dk_n = dv_n = None
+            if dkv_direct:
+                dk_home = torch.empty_like(kb)
+                dv_home = torch.empty_like(vb)
+            else:
+                fac = (torch.zeros if (skip or split_dkv > 1 or ddkv is not None)
+                       else torch.empty)
+                contrib = fac(2, b * hk * n * d, device=qb.device,
+                              dtype=torch.float32)
                 dk_n = contrib[0].view(b, hk, n, d)
                 dv_n = contrib[1].view(b, hk, d, n)
+            if not skip:
                 dq_acc_flag = dq_zeroed or info.hop != first_active
                 # dq + dk/dv kernels (sequential: their LDS footprints do
                 # not co-reside, so stream-splitting buys nothing)
                 ext.attn_bwd(qb, k_t, v_t, dob, mk, lse, delta,
-                             dq, dk_n, dv_n,
+                             None if dq_direct else dq, dk_n, dv_n,
                              scale, causal, diag, 1, win, lookback is not None,
                              softclamp_qk_sim, softclamp_value, dq_acc_flag,
-                             split_dq, 1, ddq, None)
+                             split_dq, 1, ddq, None,
+                             dq_bf=dq if dq_direct else None)
                 ext.attn_bwd(qb, k_t, v_t, dob, mk, lse, delta,
-                             dq, dk_n, dv_n,
+                             None if dq_direct else dq, dk_n, dv_n,
                              scale, causal, diag, 1, win, lookback is not None,
                              softclamp_qk_sim, softclamp_value, False,
-                             split_dkv, 2, None, ddkv)
-            acc.step(contrib, info.is_last)
+                             split_dkv, 2, None, ddkv,
+                             dk_bf=dk_home, dv_bf=dv_home)
+            if not dkv_direct:
+                acc.step(contrib, info.is_last)
 
-        dkv = acc.finish(hops)
-        dk_home = dkv[0].view(b, hk, n, d).permute(0, 2, 1, 3).contiguous()
-        dv_home = dkv[1].view(b, hk, d, n).permute(0, 3, 1, 2).contiguous()
+        if not dkv_direct:
+            dkv = acc.finish(hops)
+            dq, dk_home, dv_home = _finish_grads(
+                ext, fused, in_dtype, dq,
+                dkv[0].view(b, hk, n, d), dkv[1].view(b, hk, d, n))
+        elif dq.dtype == torch.float32:
+            dq = ext.attn_bwd_finalize(None, None, dq)[0]
 
-        return (dq.to(in_dtype), dk_home.to(in_dtype), dv_home.to(in_dtype),
+        return (dq, dk_home, dv_home,
                 None, None, None, None, None, None, None, None, None, None)
 
 
@@ -608,20 +682,36 @@ class FlashAttnOffsetFunction(Function):
         ext = hip_ext.require()
         dob = do.to(torch.bfloat16).contiguous()
         delta = ext.attn_delta(dob, out)
-        ddq = ddkv = None
+        ddkv = None
         kvt_ = (nk + 255) // 256
         if _use_desc(causal, None, q_offset, nk, kvt_ * b * hk):
             ddkv = _walk_descriptors("dkv", d, n, nk, q_offset, 1, b * hk, qb.device)
+        fused = _fused_epilogue(in_dtype)
+        if fused and ddkv is None:
+            # single-pass: both kernels emit final bf16 gradients
+            dq, dk, dv = (torch.empty_like(qb), torch.empty_like(kb),
+                          torch.empty_like(vb))
+            ext.attn_bwd(qb, kb, vb, dob, None, lse, delta, None, None, None,
+                         scale, causal, q_offset, 1, 0, False, False, 50.0,
+                         False, 1, 0, None, None,
+                         dq_bf=dq, dk_bf=dk, dv_bf=dv)
+            return dq, dk, dv, None, None, None
         fac = torch.zeros if ddkv is not None else torch.empty
-        dq = torch.empty(b, n, h, d, device=qb.device, dtype=torch.float32)
+        dq = (torch.empty_like(qb) if fused else
+              torch.empty(b, n, h, d, device=qb.device, dtype=torch.float32))
         dk_n = fac(b, hk, nk, d, device=qb.device, dtype=torch.float32)
         dv_n = fac(b, hk, d, nk, device=qb.device, dtype=torch.float32)
-        ext.attn_bwd(qb, kb, vb, dob, None, lse, delta, dq, dk_n, dv_n,
-                     scale, causal, q_offset, 1, 0, False, False, 50.0, False, 1, 0,
-                     ddq, ddkv)
-        dk = dk_n.permute(0, 2, 1, 3).contiguous()
-        dv = dv_n.permute(0, 3, 1, 2).contiguous()
-        return (dq.to(in_dtype), dk.to(in_dtype), dv.to(in_dtype), None, None, None)
+        # descriptor units cover only the dkv launch: dq stays single-pass
+        ext.attn_bwd(qb, kb, vb, dob, None, lse, delta,
+                     None if fused else dq, dk_n, dv_n,
+                     scale, causal, q_offset, 1, 0, False, False, 50.0, False, 1, 1,
+                     None, None, dq_bf=dq if fused else None)
+        ext.attn_bwd(qb, kb, vb, dob, None, lse, delta,
+                     None if fused else dq, dk_n, dv_n,
+                     scale, causal, q_offset, 1, 0, False, False, 50.0, False, 1, 2,
+                     None, ddkv)
+        dq, dk, dv = _finish_grads(ext, fused, in_dtype, dq, dk_n, dv_n)
+        return dq, dk, dv, None, None, None
 
 
 def flash_attn_offset(q, k, v, q_offset=0, causal=True):
@@ -687,17 +777,26 @@ class FlashAttnFunction(Function):
         ext = hip_ext.require()
         dob = do.to(torch.bfloat16).contiguous()
         delta = ext.attn_delta(dob, out)
-        dq = torch.empty(b, n, h, d, device=qb.device, dtype=torch.float32)
-        dk_n = torch.empty(b, hk, nk, d, device=qb.device, dtype=torch.float32)
-        dv_n = torch.empty(b, hk, d, nk, device=qb.device, dtype=torch.float32)
-        ext.attn_bwd(qb, kb, vb, dob, mk, lse, delta, dq, dk_n, dv_n,
+        fused = _fused_epilogue(in_dtype)
+        if fused:
+            # always single-pass here: the kernels emit final bf16 gradients
+            dq, dk, dv = (torch.empty_like(qb), torch.empty_like(kb),
+                          torch.empty_like(vb))
+            dq32 = dk_n = dv_n = None
+        else:
+            dq32 = torch.empty(b, n, h, d, device=qb.device, dtype=torch.float32)
+            dk_n = torch.empty(b, hk, nk, d, device=qb.device, dtype=torch.float32)
+            dv_n = torch.empty(b, hk, d, nk, device=qb.device, dtype=torch.float32)
+        ext.attn_bwd(qb, kb, vb, dob, mk, lse, delta, dq32, dk_n, dv_n,
                      scale, causal, diag, 1,
                      window if window is not None else 0, window is not None,
                      softclamp, softclamp_value, False, 1, 0, None, None,
-                     bias=biasf, bias_mat=bool(bias_mat))
-        dk = dk_n.permute(0, 2, 1, 3).contiguous()
-        dv = dv_n.permute(0, 3, 1, 2).contiguous()
-        return (dq.to(in_dtype), dk.to(in_dtype), dv.to(in_dtype),
+                     bias=biasf, bias_mat=bool(bias_mat),
+                     dq_bf=dq if fused else None, dk_bf=dk if fused else None,
+                     dv_bf=dv if fused else None)
+        if not fused:
+            dq, dk, dv = _finish_grads(ext, False, in_dtype, dq32, dk_n, dv_n)
+        return (dq, dk, dv,
                 None, None, None, None, None, None, None, None, None)
 
 
