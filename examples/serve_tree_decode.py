@@ -12,6 +12,12 @@ or single-process (no collectives, same math).  On GPU the local partial
 is the HIP decode kernel (2.6 TB/s at 128k KV — 101 us/step; `--fp8`
 halves the stream to 50 us); on CPU it
 falls back to the eager partial so this example runs anywhere.
+
+`--paged` serves a RAGGED batch from a block-table paged KV cache instead
+(`PagedKVCache` + `tree_attn_decode_paged`): every sequence has its own
+length, and each step appends the new token's K/V to the tail rank's pages
+before decoding — the cache grows page by page, nothing is reallocated.
+Works with and without `--fp8` (fused quantising append), on GPU and CPU.
 """
 
 from __future__ import annotations
@@ -34,12 +40,20 @@ def main():
     ap.add_argument("--kv-len", type=int, default=8192, help="total KV cache length")
     ap.add_argument("--heads", type=int, default=8)
     ap.add_argument("--d-head", type=int, default=64)
-    ap.add_argument("--batch", type=int, default=1)
+    ap.add_argument("--batch", type=int, default=None,
+                    help="sequences (default 1; 4 with --paged)")
     ap.add_argument("--steps", type=int, default=16, help="tokens to decode")
     ap.add_argument("--fp8", action="store_true",
                     help="serve from an e4m3-quantized KV cache (GPU only; "
                          "half the HBM stream per step)")
+    ap.add_argument("--paged", action="store_true",
+                    help="ragged batch over a paged KV cache that grows by "
+                         "one token per step")
+    ap.add_argument("--page-size", type=int, default=64,
+                    help="tokens per page with --paged (power of two, 16..256)")
     args = ap.parse_args()
+    if args.batch is None:
+        args.batch = 4 if args.paged else 1
 
     if "RANK" in os.environ and not is_distributed():
         torch.distributed.init_process_group(
@@ -49,6 +63,9 @@ def main():
     if device == "cuda":
         torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", 0)))
     dtype = torch.bfloat16 if device == "cuda" else torch.float32
+
+    if args.paged:
+        return serve_paged(args, rank, world, device, dtype)
 
     b, h, d = args.batch, args.heads, args.d_head
     n_local = args.kv_len // world
@@ -94,6 +111,63 @@ def main():
 
     if rank == 0:
         print(f"world {world}  kv {args.kv_len} ({n_local}/rank)  "
+              f"{args.steps} steps  {dt*1e6:.0f} us/token  "
+              f"out[0,0,0,:4] = {outs[-1][0,0,0,:4].float().tolist()}")
+
+
+def serve_paged(args, rank, world, device, dtype):
+    from ring_attention_amd import PagedKVCache, tree_attn_decode_paged
+
+    b, h, d, ps = args.batch, args.heads, args.d_head, args.page_size
+    # ragged batch: sequence i holds kv_len, ..., down to about kv_len / 2
+    lens = [args.kv_len - i * (args.kv_len // (2 * b)) for i in range(b)]
+    # this rank's shard [lo, hi) of every sequence of a COMMON synthetic
+    # cache (in service: filled by prefill); the LAST rank holds the tails
+    # and takes the new tokens
+    lo = [n * rank // world for n in lens]
+    hi = [n * (rank + 1) // world for n in lens]
+    local = [e - s for s, e in zip(lo, hi)]
+    tail = rank == world - 1
+
+    torch.manual_seed(1234)
+    k_full = torch.randn(b, h, args.kv_len, d, device=device, dtype=dtype)
+    v_full = torch.randn(b, h, args.kv_len, d, device=device, dtype=dtype)
+    t = max(max(local), 1)
+    k_loc = torch.zeros(b, h, t, d, device=device, dtype=dtype)
+    v_loc = torch.zeros(b, h, t, d, device=device, dtype=dtype)
+    for i in range(b):
+        k_loc[i, :, :local[i]] = k_full[i, :, lo[i]:hi[i]]
+        v_loc[i, :, :local[i]] = v_full[i, :, lo[i]:hi[i]]
+    del k_full, v_full
+
+    grow = args.steps if tail else 0
+    per_seq = [-(-(n + grow) // ps) for n in local]
+    cache = PagedKVCache(sum(per_seq), ps, h, d, b, max(max(per_seq), 1),
+                         fp8=args.fp8, device=device)
+    cache.append(k_loc, v_loc, local)          # ragged prompt prefill
+    del k_loc, v_loc
+
+    torch.manual_seed(7)
+    q = torch.randn(b, h, 1, d, device=device, dtype=dtype)
+
+    outs = []
+    t0 = time.perf_counter()
+    for step in range(args.steps):
+        # the new token's K/V go to the tail rank's pages first (stand-ins
+        # derived from q; in a real server they come from the model), then
+        # every rank decodes over its shard: 2 collective rounds per token
+        if tail:
+            cache.append(q, q.flip(-1))
+        out = tree_attn_decode_paged(q, cache)
+        outs.append(out)
+        q = out
+    if device == "cuda":
+        torch.cuda.synchronize()
+    dt = (time.perf_counter() - t0) / args.steps
+
+    if rank == 0:
+        print(f"world {world}  paged{' fp8' if args.fp8 else ''}  page {ps}  "
+              f"batch {b}  kv {lens[0]}..{lens[-1]} (+{args.steps})  "
               f"{args.steps} steps  {dt*1e6:.0f} us/token  "
               f"out[0,0,0,:4] = {outs[-1][0,0,0,:4].float().tolist()}")
 

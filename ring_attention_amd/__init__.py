@@ -19,7 +19,12 @@ from .models import (
     RingTransformer,
     apply_rotary_pos_emb,
 )
-from .tree_decode import tree_attn_decode, tree_attn_decode_fp8
+from .paged_cache import PagedKVCache
+from .tree_decode import (
+    tree_attn_decode,
+    tree_attn_decode_fp8,
+    tree_attn_decode_paged,
+)
 from .zigzag import zig_zag_attn, zig_zag_pad_seq, zig_zag_shard
 
 __version__ = "0.1.0"
@@ -44,6 +49,8 @@ __all__ = [
     "FeedForward",
     "tree_attn_decode",
     "tree_attn_decode_fp8",
+    "tree_attn_decode_paged",
+    "PagedKVCache",
     "zig_zag_attn",
     "zig_zag_pad_seq",
     "zig_zag_shard",

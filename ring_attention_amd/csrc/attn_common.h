@@ -187,6 +187,53 @@ struct DecodeMergeParams {
 
 void launch_decode_merge(const DecodeMergeParams& p, int head_dim, hipStream_t stream);
 
+// Paged KV cache (decode_paged.hip).  Pool pages are (P, HK, PS, D) with
+// PS = 1 << page_shift; key j of sequence b lives at page
+// block_table[b][j >> page_shift], row j & (PS - 1).
+struct PagedDecodeParams {
+    const void* q;          // bf16 (B, HQ, NQ, D)
+    const void* k_pages;    // bf16 or e4m3 bytes (P, HK, PS, D)
+    const void* v_pages;    // bf16 or e4m3 bytes (P, HK, PS, D)
+    const void* kscale;     // fp8 mode: e8m0 per row (P, HK, PS)
+    const void* vscale;     // fp8 mode: e8m0 per row (P, HK, PS)
+    const int* block_table; // int32 (B, max_pages); entries at or beyond
+                            // ceil(seq_len / PS) are never read
+    const int* seq_lens;    // int32 (B): tokens held per sequence (0 legal)
+    float* out;             // fp32 (S, B, HQ, NQ, D) per-chunk partials
+    float* lse;             // fp32 (S, B, HQ, NQ, 1)
+    int b, h;               // h = HQ (query heads)
+    int hk;                 // kv heads; q head qh reads kv head qh % hk
+    int nq;                 // query tokens per head (>= 1)
+    int page_shift;         // log2(page size)
+    int max_pages;          // block_table row stride
+    int num_pages;          // P: ids outside [0, P) are never dereferenced
+    int causal;             // query iq sees keys [0, seq_len - (nq-1-iq))
+    int chunk_major;        // 1 = kv chunk is the fast workgroup index
+    float scale;
+    long chunks;            // kv-split S (0 = auto from max_seq_len)
+    long max_seq_len;       // host-known upper bound of seq_lens
+};
+
+void launch_decode_partial_paged(const PagedDecodeParams& p, int head_dim, bool fp8,
+                                 hipStream_t stream);
+
+struct PagedAppendParams {
+    const void* k_new;      // bf16 (B, HK, T, D)
+    const void* v_new;      // bf16 (B, HK, T, D)
+    void* k_pages;          // bf16 or e4m3 bytes (P, HK, PS, D)
+    void* v_pages;
+    void* kscale;           // fp8 mode: e8m0 per row (P, HK, PS)
+    void* vscale;
+    const int* block_table; // int32 (B, max_pages)
+    const int* seq_lens;    // int32 (B): lengths BEFORE the append
+    const int* append_lens; // int32 (B): 0 <= append_lens[b] <= T
+    int b, hk, t;
+    int page_shift, max_pages, num_pages;
+};
+
+void launch_paged_kv_append(const PagedAppendParams& p, int head_dim, bool fp8,
+                            hipStream_t stream);
+
 struct Fp8FwdParams {
     const void* q;      // e4m3 bytes (B, Nq, H, D)
     const void* k;      // e4m3 bytes (B, Nk, H, D)

@@ -453,6 +453,150 @@ std::vector<at::Tensor> decode_merge(at::Tensor outs, at::Tensor lses) {
     return {out, lse};
 }
 
+// shared checks of the paged-cache operands; returns log2(page_size)
+static int check_paged_pool(const at::Tensor& ref, const at::Tensor& k_pages,
+                            const at::Tensor& v_pages,
+                            const std::optional<at::Tensor>& k_scales,
+                            const std::optional<at::Tensor>& v_scales,
+                            const at::Tensor& block_table, const at::Tensor& seq_lens,
+                            int64_t B, int64_t D, bool* fp8_out) {
+    TORCH_CHECK(k_pages.dim() == 4 && v_pages.dim() == 4,
+                "k_pages/v_pages must be (num_pages, HK, page_size, D)");
+    TORCH_CHECK(k_pages.is_contiguous() && v_pages.is_contiguous(),
+                "k_pages/v_pages must be contiguous");
+    TORCH_CHECK(k_pages.sizes() == v_pages.sizes()
+                && k_pages.scalar_type() == v_pages.scalar_type(),
+                "k_pages and v_pages must match in shape and dtype (dv == d)");
+    const bool fp8 = k_pages.scalar_type() == at::kByte;
+    TORCH_CHECK(fp8 || k_pages.scalar_type() == at::kBFloat16,
+                "pages must be bf16 or uint8 (e4m3 bytes)");
+    const int64_t P = k_pages.size(0), HK = k_pages.size(1), PS = k_pages.size(2);
+    TORCH_CHECK(k_pages.size(3) == D, "page head dim must equal q/k_new head dim");
+    TORCH_CHECK(D == 64 || D == 128, "head dim must be 64 or 128");
+    TORCH_CHECK(PS >= 16 && PS <= 256 && (PS & (PS - 1)) == 0,
+                "page_size must be a power of two in [16, 256] (got ", PS, ")");
+    TORCH_CHECK(P < (int64_t(1) << 31), "too many pages");
+    if (fp8) {
+        TORCH_CHECK(k_scales.has_value() && v_scales.has_value(),
+                    "fp8 pages need k_scales/v_scales");
+        for (auto* t : {&*k_scales, &*v_scales})
+            TORCH_CHECK(t->scalar_type() == at::kByte && t->is_contiguous()
+                        && t->device() == k_pages.device()
+                        && t->dim() == 3 && t->size(0) == P && t->size(1) == HK
+                        && t->size(2) == PS,
+                        "scales must be contiguous uint8 (num_pages, HK, page_size)");
+    }
+    TORCH_CHECK(block_table.scalar_type() == at::kInt && block_table.is_contiguous()
+                && block_table.dim() == 2 && block_table.size(0) == B,
+                "block_table must be contiguous int32 (B, max_pages_per_seq)");
+    TORCH_CHECK(seq_lens.scalar_type() == at::kInt && seq_lens.is_contiguous()
+                && seq_lens.dim() == 1 && seq_lens.size(0) == B,
+                "seq_lens must be contiguous int32 (B,)");
+    TORCH_CHECK(block_table.device() == ref.device() && seq_lens.device() == ref.device()
+                && k_pages.device() == ref.device() && v_pages.device() == ref.device(),
+                "pages, block_table and seq_lens must be on the same device as q/k_new");
+    TORCH_CHECK(block_table.size(1) * PS < (int64_t(1) << 31), "table too wide");
+    *fp8_out = fp8;
+    int shift = 0;
+    while ((int64_t(1) << shift) < PS) ++shift;
+    return shift;
+}
+
+std::vector<at::Tensor> decode_partial_paged(
+    at::Tensor q, at::Tensor k_pages, at::Tensor v_pages,
+    std::optional<at::Tensor> k_scales, std::optional<at::Tensor> v_scales,
+    at::Tensor block_table, at::Tensor seq_lens, int64_t max_seq_len,
+    double sm_scale, bool causal, int64_t chunks_in) {
+    // q bf16 (B,HQ,NQ,D); pages (P,HK,PS,D) bf16, or uint8 e4m3 with per-row
+    // e8m0 scales (P,HK,PS) — the page dtype selects the fp8 kernel;
+    // block_table int32 (B,max_pages), seq_lens int32 (B,).  max_seq_len is
+    // the HOST's upper bound of seq_lens (drives the kv-split; no device
+    // read).  Same output contract as decode_partial.
+    CHECK_BF16_CONTIG(q);
+    TORCH_CHECK(q.dim() == 4, "q must be (B,HQ,NQ,D)");
+    const int64_t B = q.size(0), H = q.size(1), NQ = q.size(2), D = q.size(3);
+    bool fp8 = false;
+    const int shift = check_paged_pool(q, k_pages, v_pages, k_scales, v_scales,
+                                       block_table, seq_lens, B, D, &fp8);
+    const int64_t HK = k_pages.size(1);
+    TORCH_CHECK(H % HK == 0, "q heads must be a multiple of kv heads");
+    TORCH_CHECK(max_seq_len >= 0
+                && max_seq_len <= block_table.size(1) * k_pages.size(2),
+                "max_seq_len exceeds what block_table can address");
+    int64_t waves = B * H * NQ;
+    // the dense bindings' swept kv-split heuristic (~512 keys per wave,
+    // waves capped near 8192, S <= 256) on the longest sequence
+    int64_t chunks = chunks_in > 0 ? chunks_in : std::max<int64_t>(
+        1, std::min<int64_t>(std::min<int64_t>(max_seq_len / 512 + 1, 256),
+                             8192 / std::max<int64_t>(waves, 1)));
+    TORCH_CHECK(chunks <= 65535, "chunks must fit grid.y");
+    TORCH_CHECK((waves + 3) / 4 * chunks < (int64_t(1) << 31), "grid too large");
+    auto out = at::empty({chunks, B, H, NQ, D}, q.options().dtype(at::kFloat));
+    auto lse = at::empty({chunks, B, H, NQ, 1}, q.options().dtype(at::kFloat));
+    if (waves == 0) return {out, lse};
+    PagedDecodeParams p{};
+    p.q = q.data_ptr();
+    p.k_pages = k_pages.data_ptr(); p.v_pages = v_pages.data_ptr();
+    if (fp8) { p.kscale = k_scales->data_ptr(); p.vscale = v_scales->data_ptr(); }
+    p.block_table = block_table.data_ptr<int>();
+    p.seq_lens = seq_lens.data_ptr<int>();
+    p.out = out.data_ptr<float>(); p.lse = lse.data_ptr<float>();
+    p.b = (int)B; p.h = (int)H; p.hk = (int)HK; p.nq = (int)NQ;
+    p.page_shift = shift;
+    p.max_pages = (int)block_table.size(1);
+    p.num_pages = (int)k_pages.size(0);
+    p.causal = causal ? 1 : 0;
+    // workgroup order: a batch can be ragged, so its kv chunks are the fast
+    // workgroup index (every sequence spreads over all XCDs: ragged b=8
+    // 1k..128k 601 -> 241 us); a single sequence keeps the dense kernels'
+    // order, which measured at dense speed for every page size / table.
+    // RING_ATTN_PAGED_ORDER=row|chunk forces either (A/B).
+    const char* order = std::getenv("RING_ATTN_PAGED_ORDER");
+    p.chunk_major = order && order[0] == 'r' ? 0
+                  : order && order[0] == 'c' ? 1 : (B > 1 ? 1 : 0);
+    p.scale = sm_scale > 0 ? (float)sm_scale : (float)(1.0 / std::sqrt((double)D));
+    p.chunks = chunks;
+    p.max_seq_len = max_seq_len;
+    launch_decode_partial_paged(p, (int)D, fp8, at::hip::getCurrentHIPStream());
+    TORCH_CHECK(hipGetLastError() == hipSuccess, "paged decode launch failed");
+    return {out, lse};
+}
+
+void paged_kv_append(
+    at::Tensor k_new, at::Tensor v_new, at::Tensor k_pages, at::Tensor v_pages,
+    std::optional<at::Tensor> k_scales, std::optional<at::Tensor> v_scales,
+    at::Tensor block_table, at::Tensor seq_lens, at::Tensor append_lens) {
+    // k_new/v_new bf16 (B,HK,T,D): token t < append_lens[b] of sequence b is
+    // written at position seq_lens[b] + t (seq_lens = lengths BEFORE the
+    // append; the caller advances them).  uint8 pages quantise in flight.
+    CHECK_BF16_CONTIG(k_new); CHECK_BF16_CONTIG(v_new);
+    TORCH_CHECK(k_new.dim() == 4 && k_new.sizes() == v_new.sizes(),
+                "k_new/v_new must both be (B,HK,T,D)");
+    const int64_t B = k_new.size(0), HK = k_new.size(1), T = k_new.size(2), D = k_new.size(3);
+    bool fp8 = false;
+    const int shift = check_paged_pool(k_new, k_pages, v_pages, k_scales, v_scales,
+                                       block_table, seq_lens, B, D, &fp8);
+    TORCH_CHECK(k_pages.size(1) == HK, "kv heads of k_new and the pages differ");
+    TORCH_CHECK(append_lens.scalar_type() == at::kInt && append_lens.is_contiguous()
+                && append_lens.dim() == 1 && append_lens.size(0) == B
+                && append_lens.device() == k_new.device(),
+                "append_lens must be contiguous int32 (B,) on the same device");
+    TORCH_CHECK(B * HK * T < (int64_t(1) << 33), "append too large");
+    PagedAppendParams p{};
+    p.k_new = k_new.data_ptr(); p.v_new = v_new.data_ptr();
+    p.k_pages = k_pages.data_ptr(); p.v_pages = v_pages.data_ptr();
+    if (fp8) { p.kscale = k_scales->data_ptr(); p.vscale = v_scales->data_ptr(); }
+    p.block_table = block_table.data_ptr<int>();
+    p.seq_lens = seq_lens.data_ptr<int>();
+    p.append_lens = append_lens.data_ptr<int>();
+    p.b = (int)B; p.hk = (int)HK; p.t = (int)T;
+    p.page_shift = shift;
+    p.max_pages = (int)block_table.size(1);
+    p.num_pages = (int)k_pages.size(0);
+    launch_paged_kv_append(p, (int)D, fp8, at::hip::getCurrentHIPStream());
+    TORCH_CHECK(hipGetLastError() == hipSuccess, "paged append launch failed");
+}
+
 at::Tensor attn_delta(at::Tensor dout, at::Tensor out) {
     // dout, out (B,N,H,D) bf16 -> delta fp32 (B,H,N) = rowsum(dout*out)
     CHECK_BF16_CONTIG(dout); CHECK_BF16_CONTIG(out);
@@ -509,6 +653,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::arg("vs"), py::arg("sm_scale") = -1.0, py::arg("chunks") = 0);
     mod.def("decode_merge", &ring_attn::decode_merge,
             "fused kv-chunk partial merge for decode");
+    mod.def("decode_partial_paged", &ring_attn::decode_partial_paged,
+            "CDNA4 paged KV-cache decode partial (bf16 or fp8 pages)",
+            py::arg("q"), py::arg("k_pages"), py::arg("v_pages"),
+            py::arg("k_scales"), py::arg("v_scales"), py::arg("block_table"),
+            py::arg("seq_lens"), py::arg("max_seq_len"),
+            py::arg("sm_scale") = -1.0, py::arg("causal") = false,
+            py::arg("chunks") = 0);
+    mod.def("paged_kv_append", &ring_attn::paged_kv_append,
+            "write new tokens into a paged KV cache (fused fp8 quantisation)",
+            py::arg("k_new"), py::arg("v_new"), py::arg("k_pages"),
+            py::arg("v_pages"), py::arg("k_scales"), py::arg("v_scales"),
+            py::arg("block_table"), py::arg("seq_lens"), py::arg("append_lens"));
     mod.def("attn_delta", &ring_attn::attn_delta, "fused delta = rowsum(dO*O) preprocess");
     mod.def("rotary_apply", &ring_attn::rotary_apply, "fused rotary embedding (table-driven)");
 }

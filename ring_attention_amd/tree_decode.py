@@ -148,3 +148,86 @@ def tree_attn_decode_fp8(
               * torch.exp2(vs.float() - 127.0).unsqueeze(-1))
         local_out, lse = _local_decode_partial(q, kd, vd)
     return _merge_across_ranks(local_out, lse, dtype, eps)
+
+
+def _local_paged_decode_partial(q: Tensor, cache, causal: bool = False,
+                                use_hip_kernel: bool | None = None,
+                                chunks: int = 0) -> tuple[Tensor, Tensor]:
+    """Local flash-decode partial over a PagedKVCache:
+    (out fp32 (b,h,nq,d), lse fp32 (b,h,nq,1)).
+
+    q (b, h, nq, d) with b == cache.max_seqs and d == cache.dim_head (the
+    paged path requires dv == d).  Row (b, iq) attends keys [0, limit) of
+    sequence b, limit = seq_lens[b], or with `causal`
+    max(0, seq_lens[b] - (nq - 1 - iq)): the last nq cached positions are
+    the queries' own tokens.  A row whose limit is 0 returns out == 0 with a
+    finite lse <= -1e30, so it drops out of any later merge.
+    """
+    b, h, nq, d = q.shape
+    assert b == cache.max_seqs and d == cache.dim_head
+    assert h % cache.kv_heads == 0
+    if q.is_cuda and use_hip_kernel is not False:
+        from .ops import hip_ext
+        ext = hip_ext.require()       # no eager fallback on GPU
+        kd = cache.kernel_dim
+        import torch.nn.functional as _F
+        qb = _F.pad(q, (0, kd - d)) if d != kd else q
+        outs, lses = ext.decode_partial_paged(
+            qb.to(torch.bfloat16).contiguous(),
+            cache.k_pages, cache.v_pages, cache.k_scales, cache.v_scales,
+            cache.block_table, cache.seq_lens, cache.max_seq_len,
+            d ** -0.5, causal, chunks)
+        out, lse = ext.decode_merge(outs, lses)
+        if d != kd:
+            out = out[..., :d]
+        return out, lse
+
+    # eager fallback (CPU): gather each sequence, mask by length and tail
+    scale = d ** -0.5
+    hk = cache.kv_heads
+    groups = h // hk
+    neg = -torch.finfo(torch.float32).max
+    out = q.new_zeros((b, h, nq, d), dtype=torch.float32)
+    lse = torch.full((b, h, nq, 1), neg, device=q.device, dtype=torch.float32)
+    lens = cache.host_lens
+    for i in range(b):
+        n = lens[i]
+        if n == 0:
+            continue
+        kf, vf = cache.gather(i)
+        kf = kf.float().repeat(groups, 1, 1)            # tile pairing qh % hk
+        vf = vf.float().repeat(groups, 1, 1)
+        sim = torch.einsum("hid,hjd->hij", q[i].float(), kf) * scale
+        if causal:
+            limit = n - (nq - 1 - torch.arange(nq, device=q.device))
+            masked = torch.arange(n, device=q.device)[None, :] >= limit[:, None]
+            sim = sim.masked_fill(masked[None], float("-inf"))
+        row_lse = sim.logsumexp(dim=-1, keepdim=True)   # -inf where limit <= 0
+        live = torch.isfinite(row_lse)
+        attn = torch.softmax(sim, dim=-1)
+        o = torch.einsum("hij,hjd->hid", torch.nan_to_num(attn), vf)
+        out[i] = torch.where(live, o, torch.zeros_like(o))
+        lse[i] = torch.where(live, row_lse, torch.full_like(row_lse, neg))
+    return out, lse
+
+
+@torch.no_grad()
+def tree_attn_decode_paged(
+    q: Tensor,
+    cache,
+    causal: bool = False,
+    eps: float = 1e-8,
+    use_hip_kernel: bool | None = None,
+) -> Tensor:
+    """Tree-attention decode over a paged KV cache with per-sequence lengths.
+
+    q (b, h, nq, d); `cache` is this rank's PagedKVCache holding its LOCAL
+    shard of every sequence (ragged, 0 tokens is legal; dv == d).  The local
+    partial is the HIP paged-decode kernel plus the fused chunk merge; ranks
+    merge exactly like tree_attn_decode (2 collective rounds).  Pass
+    `causal=True` only on the rank that holds the tail of the sequences: its
+    last nq cached positions are then the queries' own tokens and query iq
+    attends up to and including its own.
+    """
+    local_out, lse = _local_paged_decode_partial(q, cache, causal, use_hip_kernel)
+    return _merge_across_ranks(local_out, lse, q.dtype, eps)
