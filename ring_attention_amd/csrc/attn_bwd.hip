@@ -278,7 +278,7 @@ void attn_bwd_dq_kernel(BwdParams p) { // cap 256 VGPR, stop the 220 B/thread
         // s^T and dp^T computed PER 32-row BLOCK and packed immediately —
         // keeping all NBLK blocks' accumulators live (128 VGPRs) forced
         // scratch spills at the 256-register budget
-        uint32_t pk[DQ_NBLK * 8];
+        alignas(16) uint32_t pk[DQ_NBLK * 8];
         __builtin_amdgcn_s_setprio(1);
         #pragma unroll
         for (int kb = 0; kb < DQ_NBLK; ++kb) {
@@ -309,11 +309,12 @@ void attn_bwd_dq_kernel(BwdParams p) { // cap 256 VGPR, stop the 220 B/thread
                             x = __builtin_fmaf(s[r], scale2, -lse_i);  // fold
                         }
                         float pv = __builtin_amdgcn_exp2f(SOFTCLAMP ? x - lse_i : x);
-                        dse[e] = pv * (dp[r] - delta_i) * dtanh * P.scale;
+                        // the uniform softmax scale is applied once to the
+                        // fp32 accumulators in the epilogue
+                        dse[e] = pv * (dp[r] - delta_i);
+                        if constexpr (SOFTCLAMP) dse[e] *= dtanh;
                     }
-                    union { __hip_bfloat162 h2; uint32_t u; } cvt;
-                    cvt.h2 = __float22bfloat162_rn(float2{dse[0], dse[1]});
-                    pk[kb * 8 + x2] = cvt.u;
+                    pk[kb * 8 + x2] = pack_bf16x2(dse[0], dse[1]);
                 }
             } else {
                 #pragma unroll
@@ -346,11 +347,10 @@ void attn_bwd_dq_kernel(BwdParams p) { // cap 256 VGPR, stop the 220 B/thread
                         if (P.kmask) ok = ok && lds.kmask[par][jj - j0];
                         float pv = ok ? __builtin_amdgcn_exp2f(
                             SOFTCLAMP ? x - lse_i : x - lse_i) : 0.f;
-                        dse[e] = pv * (dp[r] - delta_i) * dtanh * P.scale;
+                        dse[e] = pv * (dp[r] - delta_i);
+                        if constexpr (SOFTCLAMP) dse[e] *= dtanh;
                     }
-                    union { __hip_bfloat162 h2; uint32_t u; } cvt;
-                    cvt.h2 = __float22bfloat162_rn(float2{dse[0], dse[1]});
-                    pk[kb * 8 + x2] = cvt.u;
+                    pk[kb * 8 + x2] = pack_bf16x2(dse[0], dse[1]);
                 }
             }
         }
@@ -359,21 +359,10 @@ void attn_bwd_dq_kernel(BwdParams p) { // cap 256 VGPR, stop the 220 B/thread
         if (t + 1 < t_hi) write_tile(par ^ 1);
         if (t + 2 < t_hi) load_tile();
 
-        // build B-operand fragments (lane = q, k = kv contiguous): pairs +2
-        uint32_t frag[DQ_NBLK * 2][4];
-        #pragma unroll
-        for (int kb = 0; kb < DQ_NBLK; ++kb)
-            #pragma unroll
-            for (int half = 0; half < 2; ++half)
-                #pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    u32x2 r = __builtin_amdgcn_permlane32_swap(
-                        pk[kb * 8 + half * 4 + c], pk[kb * 8 + half * 4 + c + 2], false, false);
-                    frag[kb * 2 + half][c] = r[0];
-                    frag[kb * 2 + half][c + 2] = r[1];
-                }
-
-        // dq^T[d][q] += K^T[d][kv] x ds^T[kv][q].  K^T A-fragments come
+        // dq^T[d][q] += K^T[d][kv] x ds^T[kv][q].  The B fragment of k-step
+        // ks (lane = q) is pk[4*ks .. 4*ks+3] as packed: its k order is
+        // kv = ks*16 + 4*lhi + {0,1,2,3,8,9,10,11} (see kperm_pair), and the
+        // K^T reads below pick their kv rows to match.  K^T A-fragments come
         // straight from the row-major swizzled k image via
         // ds_read_b64_tr_b16: lane f=l&15 of each 16-lane group fetches
         // K[kvq + (f>>2)][dg + 4*(f&3) ..+4] and the hardware
@@ -387,7 +376,10 @@ void attn_bwd_dq_kernel(BwdParams p) { // cap 256 VGPR, stop the 220 B/thread
             __builtin_amdgcn_s_setprio(1);
             // issue ALL K^T tr-reads up front (asm loads cannot be software-
             // pipelined by the scheduler, so one batched wait beats a wait
-            // per d-block), then run the whole MFMA stream
+            // per d-block), then run the whole MFMA stream.  The compiler-
+            // visible form (__builtin_amdgcn_ds_read_tr16_b64_v4bf16, waits
+            // placed by the scheduler) measured a tie with this one —
+            // profiles/README.md "VALU diet" — so the batched form stays.
             unsigned long long ktr[DBLK][DQ_NBLK * 2][2];
             #pragma unroll
             for (int db = 0; db < DBLK; ++db) {
@@ -396,7 +388,7 @@ void attn_bwd_dq_kernel(BwdParams p) { // cap 256 VGPR, stop the 220 B/thread
                 for (int ks = 0; ks < DQ_NBLK * 2; ++ks) {
                     #pragma unroll
                     for (int half = 0; half < 2; ++half) {
-                        const int kv = ks * 16 + 8 * lhi + 4 * half + (f15 >> 2);
+                        const int kv = ks * 16 + 4 * lhi + 8 * half + (f15 >> 2);
                         // swizzled element address of (kv, dg): 16B chunk
                         // c = dg/8 XORed with the row's swizzle key
                         const int c = (dg / 8) ^ (kv & (CH < 8 ? CH - 1 : 7));
@@ -417,13 +409,18 @@ void attn_bwd_dq_kernel(BwdParams p) { // cap 256 VGPR, stop the 220 B/thread
                     *(unsigned long long*)&ktf = ktr[db][ks][0];
                     *((unsigned long long*)&ktf + 1) = ktr[db][ks][1];
                     dq_acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                        ktf, *(const bf16x8*)frag[ks], dq_acc[db], 0, 0, 0);
+                        ktf, *(const bf16x8*)(pk + 4 * ks), dq_acc[db], 0, 0, 0);
                 }
             __builtin_amdgcn_s_setprio(0);
         }
     }
 
     if (!row_valid) return;
+    // the softmax scale, a uniform factor of ds, was left out of the hot
+    // loop: apply it once to this launch's finished fp32 partial, ahead of
+    // every output mode (exact for power-of-two scales)
+    #pragma unroll
+    for (int db = 0; db < DBLK; ++db) dq_acc[db] *= P.scale;
     if (P.dq_bf) {
         // fused epilogue (single-pass only, enforced by the binding): this
         // lane is the unique writer of its row, so round the finished fp32
@@ -537,6 +534,7 @@ void attn_bwd_dkv_kernel(BwdParams p) {
     f32x16 dv_acc[DBLK], dk_acc[DBLK];
     #pragma unroll
     for (int db = 0; db < DBLK; ++db) { dv_acc[db] = f32x16{}; dk_acc[db] = f32x16{}; }
+    const float scale2 = P.scale * 1.4426950408889634f;   // exp2 domain
 
     const int num_q_tiles = (int)((P.nq + QT - 1) / QT);
 
@@ -628,7 +626,9 @@ void attn_bwd_dkv_kernel(BwdParams p) {
             if (tid < QT) {
                 long gi = i0 + tid;
                 bool okl = gi <= imax_;
-                lse_st = okl ? lse_row[gi] : 0.f;
+                // exp2-domain lse: one product per q row here, not one per
+                // lane per element in the hot loop (same fp32 product)
+                lse_st = okl ? lse_row[gi] * 1.4426950408889634f : 0.f;
                 delta_st = okl ? delta_row[gi] : 0.f;
             }
             ++t_next;
@@ -648,7 +648,9 @@ void attn_bwd_dkv_kernel(BwdParams p) {
             for (int r = 0; r < TREGS; ++r) {
                 int c = tid + r * 512;
                 if (c < TPAIRS) {
-                    int jp = c % (QT / 2);
+                    // q pairs land in the dv/dk k order (kperm_pair): the
+                    // packed p/ds pairs are then the fragments as they stand
+                    int jp = kperm_pair(c % (QT / 2));
                     int d0 = (c / (QT / 2)) * 8;
                     #pragma unroll
                     for (int e = 0; e < 8; ++e) {
@@ -704,7 +706,7 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                     dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, vf[ks], dp, 0, 0, 0);
                 }
 
-                uint32_t p_pk[8], ds_pk[8];
+                alignas(16) uint32_t p_pk[8], ds_pk[8];
                 if (full_tile && col_valid) {
                     #pragma unroll
                     for (int x2 = 0; x2 < 8; ++x2) {
@@ -727,18 +729,17 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                                 x = P.softclamp_value * th * 1.4426950408889634f;
                                 dtanh = 1.f - th * th;
                             } else {
-                                x = __builtin_fmaf(s2[r], P.scale * 1.4426950408889634f,
-                                                   -lse4[r & 3] * 1.4426950408889634f);  // fold
+                                x = __builtin_fmaf(s2[r], scale2, -lse4[r & 3]);  // fold
                             }
-                            float pv = __builtin_amdgcn_exp2f(SOFTCLAMP ? x - lse4[r & 3] * 1.4426950408889634f : x);
+                            float pv = __builtin_amdgcn_exp2f(SOFTCLAMP ? x - lse4[r & 3] : x);
                             pe[e] = pv;
-                            dse[e] = pv * (dp[r] - delta4[r & 3]) * dtanh * P.scale;
+                            // the uniform softmax scale is applied once to
+                            // dk's fp32 accumulators in the epilogue
+                            dse[e] = pv * (dp[r] - delta4[r & 3]);
+                            if constexpr (SOFTCLAMP) dse[e] *= dtanh;
                         }
-                        union { __hip_bfloat162 h2; uint32_t u; } c1, c2;
-                        c1.h2 = __float22bfloat162_rn(float2{pe[0], pe[1]});
-                        c2.h2 = __float22bfloat162_rn(float2{dse[0], dse[1]});
-                        p_pk[x2] = c1.u;
-                        ds_pk[x2] = c2.u;
+                        p_pk[x2] = pack_bf16x2(pe[0], pe[1]);
+                        ds_pk[x2] = pack_bf16x2(dse[0], dse[1]);
                     }
                 } else {
                     #pragma unroll
@@ -764,7 +765,7 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                                 x = P.softclamp_value * th * 1.4426950408889634f;
                                 dtanh = 1.f - th * th;
                             } else {
-                                x = s2[r] * (P.scale * 1.4426950408889634f);
+                                x = s2[r] * scale2;
                             }
                             bool ok = col_valid && i <= imax;
                             if constexpr (BIAS) {
@@ -779,35 +780,21 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                             if (P.causal) ok = ok && (j <= qpos);
                             if (P.has_win) ok = ok && (qpos - j <= P.win);
                             if (P.kmask) ok = ok && kmask_own;
-                            float pv = ok ? __builtin_amdgcn_exp2f(x - lse4[r & 3] * 1.4426950408889634f) : 0.f;
+                            float pv = ok ? __builtin_amdgcn_exp2f(x - lse4[r & 3]) : 0.f;
                             pe[e] = pv;
-                            dse[e] = pv * (dp[r] - delta4[r & 3]) * dtanh * P.scale;
+                            dse[e] = pv * (dp[r] - delta4[r & 3]);
+                            if constexpr (SOFTCLAMP) dse[e] *= dtanh;
                         }
-                        union { __hip_bfloat162 h2; uint32_t u; } c1, c2;
-                        c1.h2 = __float22bfloat162_rn(float2{pe[0], pe[1]});
-                        c2.h2 = __float22bfloat162_rn(float2{dse[0], dse[1]});
-                        p_pk[x2] = c1.u;
-                        ds_pk[x2] = c2.u;
+                        p_pk[x2] = pack_bf16x2(pe[0], pe[1]);
+                        ds_pk[x2] = pack_bf16x2(dse[0], dse[1]);
                     }
                 }
 
-                // fragments (lane = kv, k = q contiguous)
-                uint32_t p_frag[2][4], ds_frag[2][4];
-                #pragma unroll
-                for (int half = 0; half < 2; ++half)
-                    #pragma unroll
-                    for (int c = 0; c < 2; ++c) {
-                        u32x2 r1 = __builtin_amdgcn_permlane32_swap(
-                            p_pk[half * 4 + c], p_pk[half * 4 + c + 2], false, false);
-                        p_frag[half][c] = r1[0];
-                        p_frag[half][c + 2] = r1[1];
-                        u32x2 r2 = __builtin_amdgcn_permlane32_swap(
-                            ds_pk[half * 4 + c], ds_pk[half * 4 + c + 2], false, false);
-                        ds_frag[half][c] = r2[0];
-                        ds_frag[half][c + 2] = r2[1];
-                    }
-
-                // dv^T[d][kv] += dO^T x p ; dk[kv][d] += ds^T x Q^T-read
+                // dv^T[d][kv] += dO^T x p ; dk[kv][d] += ds^T x Q^T-read.
+                // p_pk/ds_pk[4*half .. 4*half+3] (lane = kv) are the
+                // fragments of k-step `half` as packed: q rows
+                // 16*half + 4*lhi + {0,1,2,3,8,9,10,11}, the order the
+                // qt/dot images are staged in (kperm_pair)
                 #pragma unroll
                 for (int db = 0; db < DBLK; ++db)
                     #pragma unroll
@@ -818,15 +805,21 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                         bf16x8 doa = *(const bf16x8*)(lds.dot[par] + drow * QT +
                                                       ((ch ^ (drow & TM))) * 8);
                         dv_acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                            doa, *(const bf16x8*)p_frag[half], dv_acc[db], 0, 0, 0);
+                            doa, *(const bf16x8*)(p_pk + 4 * half), dv_acc[db], 0, 0, 0);
                         bf16x8 qta = *(const bf16x8*)(lds.qt[par] + drow * QT +
                                                       ((ch ^ (drow & TM))) * 8);
                         dk_acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                            *(const bf16x8*)ds_frag[half], qta, dk_acc[db], 0, 0, 0);
+                            *(const bf16x8*)(ds_pk + 4 * half), qta, dk_acc[db], 0, 0, 0);
                     }
             }
         }
     }
+
+    // the softmax scale, a uniform factor of ds, was left out of the hot
+    // loop: apply it once to this launch's finished fp32 dk partial, ahead
+    // of every output mode (exact for power-of-two scales)
+    #pragma unroll
+    for (int db = 0; db < DBLK; ++db) dk_acc[db] *= P.scale;
 
     if (P.dk_bf) {
         // fused epilogue (single-pass only, enforced by the binding): this

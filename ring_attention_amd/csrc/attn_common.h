@@ -17,6 +17,30 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef bf16_t bf16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef bf16_t bf16x2 __attribute__((ext_vector_type(2)));
+
+// two fp32 -> one packed bf16 pair (lo = a, hi = b), round-to-nearest-even.
+// The vector convert lowers to ONE v_cvt_pk_bf16_f32; the
+// __float22bfloat162_rn route costs two converts plus a shift and an or.
+__device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {
+    union { bf16x2 h; uint32_t u; } c;
+    c.h = __builtin_convertvector(f32x2{a, b}, bf16x2);
+    return c.u;
+}
+
+// Second-GEMM k order.  An MFMA sums over k, so any permutation of the k
+// slots shared by A and B leaves the product unchanged.  The score tile's C
+// layout gives lane half lhi rows (r&3) + 8*(r>>2) + 4*lhi, so the packed
+// pairs x2 = 4*half .. 4*half+3 of a 32-row block are rows
+// 16*half + 4*lhi + {0,1,2,3,8,9,10,11}.  Taking that as the k order of
+// k-step `half` makes the packed pairs the P/dS fragment as they stand; the
+// OTHER operand is staged to match: a transposed LDS image stores row pair
+// (b2 b1 b0) of each 16-row group at pair slot (b1 b2 b0), so the 16-byte
+// chunk lhi of the group holds exactly those rows.
+__device__ __forceinline__ int kperm_pair(int jp) {
+    return (jp & ~6) | ((jp & 4) >> 1) | ((jp & 2) << 1);
+}
 #endif
 
 // Must match ring_attention_amd.ops.reference.MASK_VALUE (torch.finfo(f32).min)

@@ -10,8 +10,10 @@
 //   * swapped QK^T: S^T[kv][q] = mfma(A=K, B=Q^T) so each lane holds a full
 //     slice of ONE q row's scores -> softmax is almost entirely in-register
 //     (31 VALU max/sum + one cross-half __shfl_xor), no LDS round trip.
-//   * P -> bf16 via v_cvt_pk_bf16_f32 pairs + v_permlane32_swap to build the
-//     PV B-operand fragments in-register (T12 pattern).
+//   * P -> bf16 via one v_cvt_pk_bf16_f32 per pair; the packed pairs ARE the
+//     PV B-operand fragments: the V^T image is staged in the k order the
+//     score tile's C layout produces (kperm_pair in attn_common.h), so no
+//     lane exchange is needed.
 //   * K and V^T staged in LDS with an XOR-16B swizzle (conflict-free
 //     ds_read_b128 column slices); 3-deep pipeline over DOUBLE-buffered LDS
 //     (one barrier per tile; staging overlaps the MFMAs).

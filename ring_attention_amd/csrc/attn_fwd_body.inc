@@ -148,7 +148,9 @@
         for (int r = 0; r < VREGS; ++r) {
             int c = tid + r * NTHREADS;
             if (c < VPAIRS) {
-                int jp = c % (KVBLK / 2);
+                // kv pairs land in the PV k order (kperm_pair): the packed P
+                // pairs are then the B fragments with no lane exchange
+                int jp = kperm_pair(c % (KVBLK / 2));
                 int d0 = (c / (KVBLK / 2)) * 8;
                 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
@@ -308,7 +310,7 @@
         const float m_exp = fmaxf(m_new, -1.7e38f);
         // full tiles (no softclamp) kept RAW scores: exp2(fma(s, scale2, -m))
         const float escale = (full_tile && !SOFTCLAMP) ? scale2 : 1.f;
-        uint32_t pk[NBLK * 8];                                      // packed bf16 pairs
+        alignas(16) uint32_t pk[NBLK * 8];                          // packed bf16 pairs
         float partial[NBLK * 8];
         #pragma unroll
         for (int x2 = 0; x2 < NBLK * 8; ++x2) {
@@ -317,9 +319,7 @@
             float e1 = __builtin_amdgcn_exp2f(
                 __builtin_fmaf(s[x2 >> 3][(2 * x2 + 1) & 15], escale, -m_exp));
             partial[x2] = e0 + e1;
-            union { __hip_bfloat162 h2; uint32_t u; } cvt;
-            cvt.h2 = __float22bfloat162_rn(float2{e0, e1});
-            pk[x2] = cvt.u;
+            pk[x2] = pack_bf16x2(e0, e1);
         }
         // pairwise tree instead of a 32-deep serial dependency chain
         #pragma unroll
@@ -340,26 +340,12 @@
             l_run += rowsum;
         }
 
-        // ---- build PV B-operand fragments via permlane32_swap
-        // pk[pb + x] holds the exp'd pair for kv rows (pattern):
+        // ---- PV B-operand fragments: pk[kb*8 + x] holds the exp'd pair for
+        // kv rows (pattern):
         //   x=0:(0,1)+4lhi  x=1:(2,3)+4lhi  x=2:(8,9)+4lhi   x=3:(10,11)+4lhi
         //   x=4:(16,17)+4lhi x=5:(18,19)+4lhi x=6:(24,25)+4lhi x=7:(26,27)+4lhi
-        // B fragment for k-step needs u32 slot c = kv (8*lhi + 2c, +1), so:
-        //   swap(pk[pb+h*4+c], pk[pb+h*4+c+2]) -> r0 = slot c, r1 = slot c+2
-        uint32_t frag[NBLK * 2][4];
-        #pragma unroll
-        for (int kb = 0; kb < NBLK; ++kb) {
-            #pragma unroll
-            for (int half = 0; half < 2; ++half) {
-                #pragma unroll
-                for (int c = 0; c < 2; ++c) {
-                    u32x2 r = __builtin_amdgcn_permlane32_swap(
-                        pk[kb * 8 + half * 4 + c], pk[kb * 8 + half * 4 + c + 2], false, false);
-                    frag[kb * 2 + half][c] = r[0];
-                    frag[kb * 2 + half][c + 2] = r[1];
-                }
-            }
-        }
+        // The vt image is staged in this k order (kperm_pair), so
+        // pk[4*ks .. 4*ks+3] IS the fragment of k-step ks — no lane exchange.
 
         if (stamp) P.ticks[t * 6 + 4] = __builtin_amdgcn_s_memtime();
         // ---- PV: O^T[d][q] += V^T[d][kv] P^T[kv][q]
@@ -372,7 +358,7 @@
                 int chunk = ks * 2 + lhi;
                 bf16x8 vf = *(const bf16x8*)(lds.vt[par] + drow * KVBLK + swz<KVBLK / 8>(drow, chunk) * 8);
                 o_acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                    vf, *(const bf16x8*)frag[ks], o_acc[db], 0, 0, 0);
+                    vf, *(const bf16x8*)(pk + 4 * ks), o_acc[db], 0, 0, 0);
             }
         }
         __builtin_amdgcn_s_setprio(0);
