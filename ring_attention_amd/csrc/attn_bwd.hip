@@ -23,7 +23,7 @@
 // removes the hazards structurally (profiled on MI355X: the single-kernel
 // atomic variant was LDS/atomic-bound at 35% LDS-array cycles).
 //
-// causality/striping/lookback use the same (diag, win) reduction as forward;
+// causality/striping/lookback use the forward's mask geometry (attn_mask.h);
 // softclamp backward applies the dtanh factor exactly as the oracle.
 //
 // Output layouts:
@@ -43,79 +43,21 @@
 
 namespace ring_attn {
 
-template <int CH>
-__device__ __forceinline__ int bswz(int row, int chunk) {
-    return chunk ^ (row & (CH < 8 ? CH - 1 : 7));   // see swz in attn_fwd.hip
-}
-
-__device__ __forceinline__ float bfast_tanhf(float x) {
-    float e = __builtin_amdgcn_exp2f(x * 2.885390081777927f);
-    return 1.f - 2.f * __builtin_amdgcn_rcpf(e + 1.f);
-}
-
-// ---------------------------------------------------------------------------
-// shared staging helpers (512-thread workgroups)
-// ---------------------------------------------------------------------------
-
-// [rows][D] bf16 row-major, 16B chunks XOR-swizzled within the row
-template <int D, int ROWS>
-__device__ __forceinline__ void stage_rowmajor(
-    const __bf16* gbase, long row0, long rowmax, long row_stride,
-    __bf16* lds_rm, int tid) {
-    constexpr int CH = D * 2 / 16;
-    for (int c = tid; c < ROWS * CH; c += 512) {
-        int row = c / CH, ch = c % CH;
-        long gr = row0 + row;
-        uint4 val = (gr <= rowmax) ? *(const uint4*)(gbase + gr * row_stride + ch * 8)
-                                   : uint4{0, 0, 0, 0};
-        *(uint4*)(lds_rm + row * D + bswz<D / 8>(row, ch) * 8) = val;
-    }
-}
-
-// [D][ROWS] bf16 transposed image via row-pair loads -> b32 writes.
-// Swizzle: 16B chunk of the d-row XORed with (d & TM).
-template <int D, int ROWS>
-__device__ __forceinline__ void stage_transposed(
-    const __bf16* gbase, long row0, long rowmax, long row_stride,
-    __bf16* lds_t, int tid) {
-    constexpr int TM = (ROWS / 8 - 1) < 7 ? (ROWS / 8 - 1) : 7;
-    constexpr int PAIRS = (ROWS / 2) * (D / 8);
-    for (int c = tid; c < PAIRS; c += 512) {
-        int jp = c % (ROWS / 2);
-        int d0 = (c / (ROWS / 2)) * 8;
-        long ja = row0 + jp * 2, jb = ja + 1;
-        bf16x8 va = (ja <= rowmax) ? *(const bf16x8*)(gbase + ja * row_stride + d0) : bf16x8{};
-        bf16x8 vb = (jb <= rowmax) ? *(const bf16x8*)(gbase + jb * row_stride + d0) : bf16x8{};
-        #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            int d = d0 + e;
-            int byte_off = d * ROWS * 2 + ((jp * 4) ^ ((d & TM) << 4));
-            __bf16 pair[2] = {va[e], vb[e]};
-            *(uint32_t*)((char*)lds_t + byte_off) = *(uint32_t*)pair;
-        }
-    }
-}
-
 // ---------------------------------------------------------------------------
 // dq kernel: row-parallel, forward-like (same pipeline as attn_fwd_kernel:
 // double-buffered LDS, one barrier per kv tile, running-pointer staging)
 // ---------------------------------------------------------------------------
-static constexpr int DQ_WAVES = 8;
-static constexpr int DQ_QROWS_WG = DQ_WAVES * 32;     // 256
+// Tile shapes come from attn_mask.h: ROWS_WG q rows (8 waves x 32) walk kv
+// tiles of kvblk(D).
 // The kt image is gone (K^T fragments come from the row-major k image via
 // ds_read_b64_tr_b16 — the v2 forward's V recipe, hardware-verified in
 // tools/hw_probe.hip), which frees a third of the LDS and the transpose
 // staging.  d128 stays at KVB=64: the KVB=128 variant its freed LDS allows
 // spills 280-336 B/lane into the hot loop and measured SLOWER (174 vs 204
 // TF headline) — the round-1 "fwd KVBLK=128 at d128" trap again.
-template <class F>
-__device__ __attribute__((noinline)) void dkv_noinline_call(F&& f) { f(); }
-
-template <int D> constexpr int dq_kvblk() { return D == 64 ? 128 : 64; }
-
 template <int D>
 struct DqLds {
-    static constexpr int KVB = dq_kvblk<D>();
+    static constexpr int KVB = kvblk(D);
     __align__(16) __bf16 k[2][KVB * D];    // [kv][d] swizzled
     __align__(16) __bf16 v[2][KVB * D];    // [kv][d] swizzled
     unsigned char kmask[2][KVB];
@@ -127,7 +69,7 @@ void attn_bwd_dq_kernel(BwdParams p) { // cap 256 VGPR, stop the 220 B/thread
                                        // scratch spills seen at the 128 cap
     constexpr int DBLK = D / 32;
     constexpr int KSTEPS = D / 16;
-    constexpr int DQ_KVBLK = dq_kvblk<D>();
+    constexpr int DQ_KVBLK = kvblk(D);
     constexpr int DQ_NBLK = DQ_KVBLK / 32;
 
     __shared__ DqLds<D> lds;
@@ -155,8 +97,8 @@ void attn_bwd_dq_kernel(BwdParams p) { // cap 256 VGPR, stop the 220 B/thread
     }
 
     auto dq_body = [&]() {
-    const BwdParams P = p;   // register-local copy (see dkv_noinline_call)
-    const long i = (long)qtile * DQ_QROWS_WG + wid * 32 + l31;
+    const BwdParams P = p;   // register-local copy (see noinline_call)
+    const long i = (long)qtile * ROWS_WG + wid * 32 + l31;
     const bool row_valid = i < P.nq;
     const long ic = row_valid ? i : 0;
 
@@ -169,40 +111,25 @@ void attn_bwd_dq_kernel(BwdParams p) { // cap 256 VGPR, stop the 220 B/thread
         qf[ks] = *(const bf16x8*)(qbase + ks * 16 + lhi * 8);
         dof[ks] = *(const bf16x8*)(dobase + ks * 16 + lhi * 8);
     }
-    const float lse_i = P.lse[((long)b * P.h + h) * P.nq + ic] * 1.4426950408889634f;
+    const float lse_i = P.lse[((long)b * P.h + h) * P.nq + ic] * LOG2E;
     const float delta_i = P.delta[((long)b * P.h + h) * P.nq + ic];
 
     f32x16 dq_acc[DBLK];
     #pragma unroll
     for (int db = 0; db < DBLK; ++db) dq_acc[db] = f32x16{};
 
-    const long wg_i_min = (long)qtile * DQ_QROWS_WG;
-    const long wg_i_max = min((long)(qtile + 1) * DQ_QROWS_WG, P.nq) - 1;
-    const long wg_q_min = wg_i_min * P.q_stride + P.diag;
-    const long wg_q_max = wg_i_max * P.q_stride + P.diag;
-    const long qpos_i = i * P.q_stride + P.diag;
-    const int num_kv_tiles = (int)((P.nk + DQ_KVBLK - 1) / DQ_KVBLK);
-
-    int t_lo = 0, t_hi = num_kv_tiles;
-    if (P.causal)
-        t_hi = wg_q_max < 0 ? 0 : min((long)num_kv_tiles, wg_q_max / DQ_KVBLK + 1);
-    if (P.has_win) {
-        long x = wg_q_min - P.win - DQ_KVBLK + 1;
-        t_lo = x <= 0 ? 0 : (int)((x + DQ_KVBLK - 1) / DQ_KVBLK);
-        if (t_lo > t_hi) t_lo = t_hi;
-    }
-    if (P.split > 1) {
-        // fractional split of this WG's own valid range (see attn_fwd)
-        int valid = t_hi - t_lo;
-        int per = (valid + P.split - 1) / P.split;
-        int base = t_lo;
-        t_lo = base + min(valid, (int)(blockIdx.z * per));
-        t_hi = base + min(valid, (int)((blockIdx.z + 1) * per));
-    }
-    if (!PAIRED && P.desc) {     // descriptor mode: exact unit bounds
-        t_lo = P.desc[(long)blockIdx.x * 3 + 1];
-        t_hi = P.desc[(long)blockIdx.x * 3 + 2];
-    }
+    // mask geometry (attn_mask.h): this workgroup's kv tile range
+    const Mask M = mask_of(P);
+    const long wg_i_min = (long)qtile * ROWS_WG;
+    const long wg_i_max = min((long)(qtile + 1) * ROWS_WG, P.nq) - 1;
+    const long wg_q_min = M.qpos(wg_i_min);
+    const long wg_q_max = M.qpos(wg_i_max);
+    const long qpos_i = M.qpos(i);
+    TileRange tr = M.kv_tile_range(wg_i_min, wg_i_max, P.nk, DQ_KVBLK);
+    if (P.split > 1) tr = split_share(tr, P.split, (int)blockIdx.z);
+    if (!PAIRED && P.desc)       // descriptor mode: exact unit bounds
+        tr = {P.desc[(long)blockIdx.x * 3 + 1], P.desc[(long)blockIdx.x * 3 + 2]};
+    const int t_lo = tr.lo, t_hi = tr.hi;
 
     // staging: K + V row chunks, K^T pairs, running pointers
     constexpr int CH = D * 2 / 16;
@@ -249,14 +176,14 @@ void attn_bwd_dq_kernel(BwdParams p) { // cap 256 VGPR, stop the 220 B/thread
             int c = tid + r * 512;
             if (c < KCHUNKS) {
                 int row = c / CH, ch = c % CH;
-                *(uint4*)(lds.k[par] + row * D + bswz<D / 8>(row, ch) * 8) = kst[r];
-                *(uint4*)(lds.v[par] + row * D + bswz<D / 8>(row, ch) * 8) = vst[r];
+                *(uint4*)(lds.k[par] + row * D + swz<D / 8>(row, ch) * 8) = kst[r];
+                *(uint4*)(lds.v[par] + row * D + swz<D / 8>(row, ch) * 8) = vst[r];
             }
         }
         if (mbase && tid < DQ_KVBLK) lds.kmask[par][tid] = mst;
     };
 
-    const float scale2 = P.scale * 1.4426950408889634f;   // exp2 domain
+    const float scale2 = P.scale * LOG2E;   // exp2 domain
     if (t_lo < t_hi) {
         load_tile();
         write_tile(t_lo & 1);
@@ -269,8 +196,7 @@ void attn_bwd_dq_kernel(BwdParams p) { // cap 256 VGPR, stop the 220 B/thread
         const long jmax = min(j0 + DQ_KVBLK, P.nk) - 1;
         const bool full_tile = !BIAS &&
             (jmax - j0 == DQ_KVBLK - 1) &&
-            (!P.causal || jmax <= wg_q_min) &&
-            (!P.has_win || (wg_q_max - j0) <= P.win) &&
+            M.uncut(wg_q_min, wg_q_max, j0, jmax) &&
             !P.kmask;
 
         __syncthreads();
@@ -287,8 +213,8 @@ void attn_bwd_dq_kernel(BwdParams p) { // cap 256 VGPR, stop the 220 B/thread
             #pragma unroll
             for (int ks = 0; ks < KSTEPS; ++ks) {
                 int chunk = ks * 2 + lhi;
-                bf16x8 kfr = *(const bf16x8*)(lds.k[par] + krow * D + bswz<D / 8>(krow, chunk) * 8);
-                bf16x8 vfr = *(const bf16x8*)(lds.v[par] + krow * D + bswz<D / 8>(krow, chunk) * 8);
+                bf16x8 kfr = *(const bf16x8*)(lds.k[par] + krow * D + swz<D / 8>(krow, chunk) * 8);
+                bf16x8 vfr = *(const bf16x8*)(lds.v[par] + krow * D + swz<D / 8>(krow, chunk) * 8);
                 s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfr, qf[ks], s, 0, 0, 0);
                 dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfr, dof[ks], dp, 0, 0, 0);
             }
@@ -302,8 +228,8 @@ void attn_bwd_dq_kernel(BwdParams p) { // cap 256 VGPR, stop the 220 B/thread
                         float x, dtanh = 1.f;
                         if constexpr (SOFTCLAMP) {
                             float inv_v = __builtin_amdgcn_rcpf(P.softclamp_value);
-                            float th = bfast_tanhf(s[r] * P.scale * inv_v);
-                            x = P.softclamp_value * th * 1.4426950408889634f;
+                            float th = fast_tanhf(s[r] * P.scale * inv_v);
+                            x = P.softclamp_value * th * LOG2E;
                             dtanh = 1.f - th * th;
                         } else {
                             x = __builtin_fmaf(s[r], scale2, -lse_i);  // fold
@@ -327,8 +253,8 @@ void attn_bwd_dq_kernel(BwdParams p) { // cap 256 VGPR, stop the 220 B/thread
                         float x, dtanh = 1.f;
                         if constexpr (SOFTCLAMP) {
                             float inv_v = __builtin_amdgcn_rcpf(P.softclamp_value);
-                            float th = bfast_tanhf(s[r] * P.scale * inv_v);
-                            x = P.softclamp_value * th * 1.4426950408889634f;
+                            float th = fast_tanhf(s[r] * P.scale * inv_v);
+                            x = P.softclamp_value * th * LOG2E;
                             dtanh = 1.f - th * th;
                         } else {
                             x = s[r] * scale2;
@@ -339,11 +265,10 @@ void attn_bwd_dq_kernel(BwdParams p) { // cap 256 VGPR, stop the 220 B/thread
                                 const long bi = P.bias_mat
                                     ? (((long)b * P.h + h) * P.nq + ic) * P.nk + jj
                                     : ((long)b * P.h + h) * P.nk + jj;
-                                x += P.bias[bi] * 1.4426950408889634f;
+                                x += P.bias[bi] * LOG2E;
                             }
                         }
-                        if (P.causal) ok = ok && (jj <= qpos_i);
-                        if (P.has_win) ok = ok && (qpos_i - jj <= P.win);
+                        ok = M.attends(qpos_i, jj, ok);
                         if (P.kmask) ok = ok && lds.kmask[par][jj - j0];
                         float pv = ok ? __builtin_amdgcn_exp2f(
                             SOFTCLAMP ? x - lse_i : x - lse_i) : 0.f;
@@ -461,9 +386,8 @@ void attn_bwd_dq_kernel(BwdParams p) { // cap 256 VGPR, stop the 220 B/thread
 // ---------------------------------------------------------------------------
 // dk/dv kernel: column-parallel, K/V resident in registers
 // ---------------------------------------------------------------------------
-static constexpr int BWD_WAVES = 8;
-static constexpr int KVROWS_WAVE = 32;
-static constexpr int KVROWS_WG = BWD_WAVES * KVROWS_WAVE;   // 256
+static constexpr int KVROWS_WAVE = 32;   // 8 waves own the ROWS_WG kv rows
+static_assert(ROWS_WG == 8 * KVROWS_WAVE);
 
 template <int D, int QT>
 struct DkvLds {
@@ -514,8 +438,8 @@ void attn_bwd_dkv_kernel(BwdParams p) {
     auto dkv_body = [&]() {
     const BwdParams P = p;   // register-local copy: the noinline frame would
                              // otherwise re-read fields through scratch
-    const long j0_wg = (long)kvtile * KVROWS_WG;
-    const long jmax = min(j0_wg + KVROWS_WG, P.nk) - 1;
+    const long j0_wg = (long)kvtile * ROWS_WG;
+    const long jmax = min(j0_wg + ROWS_WG, P.nk) - 1;
     const long j = j0_wg + wid * KVROWS_WAVE + l31;
     const bool col_valid = j <= jmax;
     const long jc = col_valid ? j : j0_wg;
@@ -534,9 +458,9 @@ void attn_bwd_dkv_kernel(BwdParams p) {
     f32x16 dv_acc[DBLK], dk_acc[DBLK];
     #pragma unroll
     for (int db = 0; db < DBLK; ++db) { dv_acc[db] = f32x16{}; dk_acc[db] = f32x16{}; }
-    const float scale2 = P.scale * 1.4426950408889634f;   // exp2 domain
+    const float scale2 = P.scale * LOG2E;   // exp2 domain
 
-    const int num_q_tiles = (int)((P.nq + QT - 1) / QT);
+    const Mask M = mask_of(P);
 
     for (int g = 0; g < P.group; ++g) {
         // group boundary barrier: the previous group's last tile is still
@@ -550,33 +474,13 @@ void attn_bwd_dkv_kernel(BwdParams p) {
         const __bf16* qg = (const __bf16*)P.q + ((long)b * P.nq) * P.h * D + (long)h * D;
         const __bf16* dog = (const __bf16*)P.dout + ((long)b * P.nq) * P.h * D + (long)h * D;
 
-        int t0 = 0, t1 = num_q_tiles;
-        if (P.causal) {
-            // need qpos(i) >= j0_wg  =>  i >= (j0_wg - diag) / q_stride
-            long i_min_needed = (j0_wg - P.diag + P.q_stride - 1) / P.q_stride;
-            if (i_min_needed > 0) t0 = (int)(i_min_needed / QT);
-        }
-        if (P.has_win) {
-            // need qpos(i) <= jmax + win  =>  i <= (jmax + win - diag) / q_stride
-            long num = jmax + P.win - P.diag;
-            long i_max_needed = num < 0 ? -1 : num / P.q_stride;
-            if (i_max_needed < (long)num_q_tiles * QT)
-                t1 = (int)min((long)num_q_tiles,
-                              i_max_needed < 0 ? 0 : i_max_needed / QT + 1);
-        }
-        if (P.split > 1) {
-            // grid.z takes a fractional share of this WG's own valid q walk
-            // (a global-range slice is skewed against the causal trapezoid)
-            int valid = t1 > t0 ? t1 - t0 : 0;
-            int per = (valid + P.split - 1) / P.split;
-            int base = t0;
-            t0 = base + min(valid, (int)(blockIdx.z * per));
-            t1 = base + min(valid, (int)((blockIdx.z + 1) * per));
-        }
-        if (!PAIRED && P.desc) {   // descriptor mode: exact unit bounds
-            t0 = P.desc[(long)blockIdx.x * 3 + 1];
-            t1 = P.desc[(long)blockIdx.x * 3 + 2];
-        }
+        // mask geometry (attn_mask.h): the q tiles this workgroup's keys
+        // are attended from; grid.z takes a share of that walk
+        TileRange tr = M.q_tile_range(j0_wg, jmax, P.nq, QT);
+        if (P.split > 1) tr = split_share(tr, P.split, (int)blockIdx.z);
+        if (!PAIRED && P.desc)     // descriptor mode: exact unit bounds
+            tr = {P.desc[(long)blockIdx.x * 3 + 1], P.desc[(long)blockIdx.x * 3 + 2]};
+        const int t0 = tr.lo, t1 = tr.hi;
 
         // ---- T14 pipeline: per-thread staging registers
         constexpr int CH = D * 2 / 16;
@@ -628,7 +532,7 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                 bool okl = gi <= imax_;
                 // exp2-domain lse: one product per q row here, not one per
                 // lane per element in the hot loop (same fp32 product)
-                lse_st = okl ? lse_row[gi] * 1.4426950408889634f : 0.f;
+                lse_st = okl ? lse_row[gi] * LOG2E : 0.f;
                 delta_st = okl ? delta_row[gi] : 0.f;
             }
             ++t_next;
@@ -640,8 +544,8 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                 int c = tid + r * 512;
                 if (c < QCHUNKS) {
                     int row = c / CH, ch = c % CH;
-                    *(uint4*)(lds.q[par] + row * D + bswz<D / 8>(row, ch) * 8) = qst[r];
-                    *(uint4*)(lds.do_[par] + row * D + bswz<D / 8>(row, ch) * 8) = dost[r];
+                    *(uint4*)(lds.q[par] + row * D + swz<D / 8>(row, ch) * 8) = qst[r];
+                    *(uint4*)(lds.do_[par] + row * D + swz<D / 8>(row, ch) * 8) = dost[r];
                 }
             }
             #pragma unroll
@@ -679,12 +583,9 @@ void attn_bwd_dkv_kernel(BwdParams p) {
             const int par = t & 1;
             const long i0 = (long)t * QT;
             const long imax = min(i0 + QT, P.nq) - 1;
-            const long q_lo = i0 * P.q_stride + P.diag;
-            const long q_hi = imax * P.q_stride + P.diag;
             const bool full_tile = !BIAS &&
                 (imax - i0 == QT - 1) &&
-                (!P.causal || q_lo >= jmax) &&
-                (!P.has_win || ((q_hi - j0_wg) <= P.win)) &&
+                M.uncut(M.qpos(i0), M.qpos(imax), j0_wg, jmax) &&
                 !P.kmask;
 
             __syncthreads();
@@ -700,8 +601,8 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                 for (int ks = 0; ks < KSTEPS; ++ks) {
                     int qrow = qb * 32 + l31;
                     int chunk = ks * 2 + lhi;
-                    bf16x8 qa = *(const bf16x8*)(lds.q[par] + qrow * D + bswz<D / 8>(qrow, chunk) * 8);
-                    bf16x8 da = *(const bf16x8*)(lds.do_[par] + qrow * D + bswz<D / 8>(qrow, chunk) * 8);
+                    bf16x8 qa = *(const bf16x8*)(lds.q[par] + qrow * D + swz<D / 8>(qrow, chunk) * 8);
+                    bf16x8 da = *(const bf16x8*)(lds.do_[par] + qrow * D + swz<D / 8>(qrow, chunk) * 8);
                     s2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa, kf[ks], s2, 0, 0, 0);
                     dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, vf[ks], dp, 0, 0, 0);
                 }
@@ -725,8 +626,8 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                             float x, dtanh = 1.f;
                             if constexpr (SOFTCLAMP) {
                                 float inv_v = __builtin_amdgcn_rcpf(P.softclamp_value);
-                                float th = bfast_tanhf(s2[r] * P.scale * inv_v);
-                                x = P.softclamp_value * th * 1.4426950408889634f;
+                                float th = fast_tanhf(s2[r] * P.scale * inv_v);
+                                x = P.softclamp_value * th * LOG2E;
                                 dtanh = 1.f - th * th;
                             } else {
                                 x = __builtin_fmaf(s2[r], scale2, -lse4[r & 3]);  // fold
@@ -761,8 +662,8 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                             float x, dtanh = 1.f;
                             if constexpr (SOFTCLAMP) {
                                 float inv_v = __builtin_amdgcn_rcpf(P.softclamp_value);
-                                float th = bfast_tanhf(s2[r] * P.scale * inv_v);
-                                x = P.softclamp_value * th * 1.4426950408889634f;
+                                float th = fast_tanhf(s2[r] * P.scale * inv_v);
+                                x = P.softclamp_value * th * LOG2E;
                                 dtanh = 1.f - th * th;
                             } else {
                                 x = s2[r] * scale2;
@@ -773,12 +674,10 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                                     const long bi = P.bias_mat
                                         ? (((long)b * P.h + h) * P.nq + i) * P.nk + j
                                         : ((long)b * P.h + h) * P.nk + j;
-                                    x += P.bias[bi] * 1.4426950408889634f;
+                                    x += P.bias[bi] * LOG2E;
                                 }
                             }
-                            long qpos = i * P.q_stride + P.diag;
-                            if (P.causal) ok = ok && (j <= qpos);
-                            if (P.has_win) ok = ok && (qpos - j <= P.win);
+                            ok = M.attends(M.qpos(i), j, ok);
                             if (P.kmask) ok = ok && kmask_own;
                             float pv = ok ? __builtin_amdgcn_exp2f(x - lse4[r & 3]) : 0.f;
                             pe[e] = pv;
@@ -836,8 +735,8 @@ void attn_bwd_dkv_kernel(BwdParams p) {
         // tensors share the one staged store loop.)
         constexpr int ECH = D / 8;
         __bf16* stg_dk = (__bf16*)&lds;
-        __bf16* stg_dv = stg_dk + KVROWS_WG * D;
-        static_assert(sizeof(DkvLds<D, QT>) >= 2 * KVROWS_WG * D * sizeof(__bf16));
+        __bf16* stg_dv = stg_dk + ROWS_WG * D;
+        static_assert(sizeof(DkvLds<D, QT>) >= 2 * ROWS_WG * D * sizeof(__bf16));
         const int wrow0 = wid * KVROWS_WAVE;
         const long orow_stride = (long)P.hk * D;
         __bf16* dkb = (__bf16*)P.dk_bf + ((long)b * P.nk) * orow_stride + (long)hkh * D;
@@ -849,7 +748,7 @@ void attn_bwd_dkv_kernel(BwdParams p) {
             for (int r = 0; r < 16; ++r) {
                 int row = wrow0 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
                 int d = db * 32 + l31;
-                stg_dk[row * D + bswz<ECH>(row, d / 8) * 8 + (d & 7)] = (__bf16)dk_acc[db][r];
+                stg_dk[row * D + swz<ECH>(row, d / 8) * 8 + (d & 7)] = (__bf16)dk_acc[db][r];
             }
         {
             // dv^T regs 4g..4g+3 are 4 consecutive d of this lane's kv row
@@ -860,7 +759,7 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                 for (int g = 0; g < 4; ++g) {
                     f32x4 v4 = {dv_acc[db][4 * g], dv_acc[db][4 * g + 1],
                                 dv_acc[db][4 * g + 2], dv_acc[db][4 * g + 3]};
-                    *(bf16x4*)(stg_dv + row * D + bswz<ECH>(row, db * 4 + g) * 8 + 4 * lhi) =
+                    *(bf16x4*)(stg_dv + row * D + swz<ECH>(row, db * 4 + g) * 8 + 4 * lhi) =
                         __builtin_convertvector(v4, bf16x4);
                 }
         }
@@ -870,7 +769,7 @@ void attn_bwd_dkv_kernel(BwdParams p) {
             int row = wrow0 + c / ECH, ch = c % ECH;
             long kvrow = j0_wg + row;
             if (kvrow <= jmax) {
-                int so = row * D + bswz<ECH>(row, ch) * 8;
+                int so = row * D + swz<ECH>(row, ch) * 8;
                 *(uint4*)(dkb + kvrow * orow_stride + ch * 8) = *(const uint4*)(stg_dk + so);
                 *(uint4*)(dvb + kvrow * orow_stride + ch * 8) = *(const uint4*)(stg_dv + so);
             }
@@ -913,7 +812,7 @@ void attn_bwd_dkv_kernel(BwdParams p) {
     // (measured headline +4%, causal +17-24%); d128 is better DIRECT for
     // both forms (paired: 125 -> 138 TF causal 8k — the same value-copy
     // preference as the d128 fwd/dq bodies), so only d64 takes the call
-    if constexpr (D == 64) dkv_noinline_call(dkv_body);
+    if constexpr (D == 64) noinline_call(dkv_body);
     else dkv_body();
     }  // pair loop
 }
@@ -921,7 +820,7 @@ void attn_bwd_dkv_kernel(BwdParams p) {
 void launch_attn_bwd_dq(const BwdParams& p, int head_dim, hipStream_t stream) {
     dim3 block(512);
     int z = p.split > 1 ? p.split : 1;
-    long qt_ = (p.nq + DQ_QROWS_WG - 1) / DQ_QROWS_WG;
+    long qt_ = ceil_div(p.nq, ROWS_WG);
     if (p.desc) qt_ = p.n_units;
     else if (p.paired) qt_ = (qt_ + 1) / 2;
     dim3 grid_dq(qt_, p.b * p.h, z);
@@ -962,39 +861,39 @@ void launch_attn_bwd_dq(const BwdParams& p, int head_dim, hipStream_t stream) {
 void launch_attn_bwd_dkv(const BwdParams& p, int head_dim, hipStream_t stream) {
     dim3 block(512);
     int z = p.split > 1 ? p.split : 1;
-    long kt_ = (p.nk + KVROWS_WG - 1) / KVROWS_WG;
+    long kt_ = ceil_div(p.nk, ROWS_WG);
     if (p.desc) kt_ = p.n_units;
     else if (p.paired) kt_ = (kt_ + 1) / 2;
     dim3 grid_dkv(kt_, p.b * p.hk, z);
     const bool pr = p.paired > 0;
     if (p.bias) {   // bias runs unpaired (bindings force paired=0)
         if (head_dim == 64) {
-            if (p.softclamp) hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, 64, true, false, true>), grid_dkv, block, 0, stream, p);
-            else hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, 64, false, false, true>), grid_dkv, block, 0, stream, p);
+            if (p.softclamp) hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, DKV_QT, true, false, true>), grid_dkv, block, 0, stream, p);
+            else hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, DKV_QT, false, false, true>), grid_dkv, block, 0, stream, p);
         } else if (head_dim == 128) {
-            if (p.softclamp) hipLaunchKernelGGL((attn_bwd_dkv_kernel<128, 64, true, false, true>), grid_dkv, block, 0, stream, p);
-            else hipLaunchKernelGGL((attn_bwd_dkv_kernel<128, 64, false, false, true>), grid_dkv, block, 0, stream, p);
+            if (p.softclamp) hipLaunchKernelGGL((attn_bwd_dkv_kernel<128, DKV_QT, true, false, true>), grid_dkv, block, 0, stream, p);
+            else hipLaunchKernelGGL((attn_bwd_dkv_kernel<128, DKV_QT, false, false, true>), grid_dkv, block, 0, stream, p);
         } else {
-            if (p.softclamp) hipLaunchKernelGGL((attn_bwd_dkv_kernel<32, 64, true, false, true>), grid_dkv, block, 0, stream, p);
-            else hipLaunchKernelGGL((attn_bwd_dkv_kernel<32, 64, false, false, true>), grid_dkv, block, 0, stream, p);
+            if (p.softclamp) hipLaunchKernelGGL((attn_bwd_dkv_kernel<32, DKV_QT, true, false, true>), grid_dkv, block, 0, stream, p);
+            else hipLaunchKernelGGL((attn_bwd_dkv_kernel<32, DKV_QT, false, false, true>), grid_dkv, block, 0, stream, p);
         }
         return;
     }
     if (head_dim == 64) {
-        if (p.softclamp) if (pr) hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, 64, true, true>), grid_dkv, block, 0, stream, p);
-        else hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, 64, true, false>), grid_dkv, block, 0, stream, p);
-        else if (pr) hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, 64, false, true>), grid_dkv, block, 0, stream, p);
-        else hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, 64, false, false>), grid_dkv, block, 0, stream, p);
+        if (p.softclamp) if (pr) hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, DKV_QT, true, true>), grid_dkv, block, 0, stream, p);
+        else hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, DKV_QT, true, false>), grid_dkv, block, 0, stream, p);
+        else if (pr) hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, DKV_QT, false, true>), grid_dkv, block, 0, stream, p);
+        else hipLaunchKernelGGL((attn_bwd_dkv_kernel<64, DKV_QT, false, false>), grid_dkv, block, 0, stream, p);
     } else if (head_dim == 128) {
-        if (p.softclamp) if (pr) hipLaunchKernelGGL((attn_bwd_dkv_kernel<128, 64, true, true>), grid_dkv, block, 0, stream, p);
-        else hipLaunchKernelGGL((attn_bwd_dkv_kernel<128, 64, true, false>), grid_dkv, block, 0, stream, p);
-        else if (pr) hipLaunchKernelGGL((attn_bwd_dkv_kernel<128, 64, false, true>), grid_dkv, block, 0, stream, p);
-        else hipLaunchKernelGGL((attn_bwd_dkv_kernel<128, 64, false, false>), grid_dkv, block, 0, stream, p);
+        if (p.softclamp) if (pr) hipLaunchKernelGGL((attn_bwd_dkv_kernel<128, DKV_QT, true, true>), grid_dkv, block, 0, stream, p);
+        else hipLaunchKernelGGL((attn_bwd_dkv_kernel<128, DKV_QT, true, false>), grid_dkv, block, 0, stream, p);
+        else if (pr) hipLaunchKernelGGL((attn_bwd_dkv_kernel<128, DKV_QT, false, true>), grid_dkv, block, 0, stream, p);
+        else hipLaunchKernelGGL((attn_bwd_dkv_kernel<128, DKV_QT, false, false>), grid_dkv, block, 0, stream, p);
     } else if (head_dim == 32) {
-        if (p.softclamp) if (pr) hipLaunchKernelGGL((attn_bwd_dkv_kernel<32, 64, true, true>), grid_dkv, block, 0, stream, p);
-        else hipLaunchKernelGGL((attn_bwd_dkv_kernel<32, 64, true, false>), grid_dkv, block, 0, stream, p);
-        else if (pr) hipLaunchKernelGGL((attn_bwd_dkv_kernel<32, 64, false, true>), grid_dkv, block, 0, stream, p);
-        else hipLaunchKernelGGL((attn_bwd_dkv_kernel<32, 64, false, false>), grid_dkv, block, 0, stream, p);
+        if (p.softclamp) if (pr) hipLaunchKernelGGL((attn_bwd_dkv_kernel<32, DKV_QT, true, true>), grid_dkv, block, 0, stream, p);
+        else hipLaunchKernelGGL((attn_bwd_dkv_kernel<32, DKV_QT, true, false>), grid_dkv, block, 0, stream, p);
+        else if (pr) hipLaunchKernelGGL((attn_bwd_dkv_kernel<32, DKV_QT, false, true>), grid_dkv, block, 0, stream, p);
+        else hipLaunchKernelGGL((attn_bwd_dkv_kernel<32, DKV_QT, false, false>), grid_dkv, block, 0, stream, p);
     } else {
         __builtin_trap();
     }

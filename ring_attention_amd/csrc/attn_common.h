@@ -8,6 +8,8 @@
 #include <hip/hip_bf16.h>
 #endif
 
+#include "attn_mask.h"
+
 namespace ring_attn {
 
 #ifdef __HIPCC__
@@ -41,6 +43,43 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {
 __device__ __forceinline__ int kperm_pair(int jp) {
     return (jp & ~6) | ((jp & 4) >> 1) | ((jp & 2) << 1);
 }
+
+// XOR swizzle of a 16-byte chunk index within a row of CH chunks:
+// chunk' = chunk ^ (row & 7).  Applied identically on the staging write and
+// the fragment read, so the LDS image is consistent (both-sides rule).
+template <int CH>
+__device__ __forceinline__ int swz(int row, int chunk) {
+    // swizzle mask must stay inside the row: CH chunks per row (CH-1 when
+    // CH <= 8; wider rows keep the measured 8-slot spread)
+    return chunk ^ (row & (CH < 8 ? CH - 1 : 7));
+}
+
+// fast tanh from builtins: tanh(x) = 1 - 2/(exp2(2x*log2e) + 1); avoids the
+// libm tanhf whose inlined body injects v_div_* sequences into the hot loop
+__device__ __forceinline__ float fast_tanhf(float x) {
+    float e = __builtin_amdgcn_exp2f(x * 2.885390081777927f);   // 2*log2(e)
+    return 1.f - 2.f * __builtin_amdgcn_rcpf(e + 1.f);
+}
+
+// cross-half (lane <-> lane^32) exchange via v_permlane32_swap — pure VALU,
+// no LDS round trip (a __shfl_xor(x, 32) lowers to ds_bpermute + addressing)
+__device__ __forceinline__ float cross_half(float x) {
+    union { float f; unsigned u; } c; c.f = x;
+    u32x2 r = __builtin_amdgcn_permlane32_swap(c.u, c.u, false, false);
+    // r0 = {lo: own lo, hi: own lo}; r1 = {lo: own hi, hi: own hi}
+    union { unsigned u; float f; } lo, hi; lo.u = r[0]; hi.u = r[1];
+    // lanes < 32 want the partner's value = own hi-half's value = r1.lo;
+    // lanes >= 32 want r0.hi = own lo-half's value — both are "the other
+    // half's x" exactly when we select r1 on lo lanes and r0 on hi lanes
+    return (threadIdx.x & 32) ? lo.f : hi.f;
+}
+
+// a noinline frame confines register allocation to the body it wraps
+template <class F>
+__device__ __attribute__((noinline)) void noinline_call(F&& f) { f(); }
+
+static constexpr float LOG2E = 1.4426950408889634f;
+static constexpr float LN2 = 0.6931471805599453f;
 #endif
 
 // Must match ring_attention_amd.ops.reference.MASK_VALUE (torch.finfo(f32).min)

@@ -17,10 +17,10 @@
 //   * K and V^T staged in LDS with an XOR-16B swizzle (conflict-free
 //     ds_read_b128 column slices); 3-deep pipeline over DOUBLE-buffered LDS
 //     (one barrier per tile; staging overlaps the MFMAs).
-//   * causality, striping and lookback reduce to integers: with
-//     qpos(i) = i*q_stride + diag, attend(i,j) <=> j <= qpos(i) AND
-//     qpos(i) - j <= win (host folds ring-rank offsets / layout strides;
-//     q_stride > 1 expresses a striped q shard against gathered global KV).
+//   * causality, striping and lookback reduce to integers (attn_mask.h holds
+//     the algebra): attend(i,j) <=> j <= qpos(i) AND qpos(i) - j <= win, with
+//     qpos affine in i (host folds ring-rank offsets / layout strides; a
+//     stride > 1 expresses a striped q shard against gathered global KV).
 //   * resume contract: fp32 o_acc (B,H,D,Nq transposed scratch), m, l
 //     (B,H,Nq) persist between ring hops; IS_FIRST initializes instead of
 //     loading, IS_LAST normalizes and emits bf16 out (B,Nq,H,D) + lse.
@@ -43,57 +43,22 @@ namespace ring_attn {
 // ---------------------------------------------------------------------------
 // geometry
 // ---------------------------------------------------------------------------
-// QROWS_WG = 256 (8 waves x 32 rows), KVBLK = 64
+// tile shapes come from attn_mask.h: 256 q rows per workgroup (8 waves x 32
+// rows), kv tile kvblk(D)
 static constexpr int WAVES = 8;          // 8-wave WGs: the 2-waves/SIMD paired
 static constexpr int QROWS_WAVE = 32;    // regime (4-wave variant measured slower)
-static constexpr int QROWS_WG = WAVES * QROWS_WAVE;
-template <int D> constexpr int fwd_kvblk() { return D == 64 ? 128 : 64; }  // LDS budget
+static constexpr int QROWS_WG = ROWS_WG;
+static_assert(QROWS_WG == WAVES * QROWS_WAVE);
 static constexpr int NTHREADS = WAVES * 64;
-
-// XOR swizzle of a 16-byte chunk index within a row (row stride D*2 bytes):
-// chunk' = chunk ^ (row & 7).  Applied identically on the staging write and
-// the fragment read, so the LDS image is consistent (both-sides rule).
-template <int CH>
-__device__ __forceinline__ int swz(int row, int chunk) {
-    // swizzle mask must stay inside the row: CH chunks per row (CH-1 when
-    // CH <= 8; wider rows keep the measured 8-slot spread)
-    return chunk ^ (row & (CH < 8 ? CH - 1 : 7));
-}
-
-// fast tanh from builtins: tanh(x) = 1 - 2/(exp2(2x*log2e) + 1); avoids the
-// libm tanhf whose inlined body injects v_div_* sequences into the hot loop
-__device__ __forceinline__ float fast_tanhf(float x) {
-    float e = __builtin_amdgcn_exp2f(x * 2.885390081777927f);   // 2*log2(e)
-    return 1.f - 2.f * __builtin_amdgcn_rcpf(e + 1.f);
-}
-
-// cross-half (lane <-> lane^32) exchange via v_permlane32_swap — pure VALU,
-// no LDS round trip (a __shfl_xor(x, 32) lowers to ds_bpermute + addressing)
-__device__ __forceinline__ float cross_half(float x) {
-    union { float f; unsigned u; } c; c.f = x;
-    u32x2 r = __builtin_amdgcn_permlane32_swap(c.u, c.u, false, false);
-    // r0 = {lo: own lo, hi: own lo}; r1 = {lo: own hi, hi: own hi}
-    union { unsigned u; float f; } lo, hi; lo.u = r[0]; hi.u = r[1];
-    // lanes < 32 want the partner's value = own hi-half's value = r1.lo;
-    // lanes >= 32 want r0.hi = own lo-half's value — both are "the other
-    // half's x" exactly when we select r1 on lo lanes and r0 on hi lanes
-    return (threadIdx.x & 32) ? lo.f : hi.f;
-}
 
 template <int D>
 struct FwdLds {
-    static constexpr int KVB = fwd_kvblk<D>();
+    static constexpr int KVB = kvblk(D);
     // double-buffered: K tile [kv][D] + V^T tile [d][kv], 16B-chunk swizzled
     __align__(16) __bf16 k[2][KVB * D];
     __align__(16) __bf16 vt[2][D * KVB];
     unsigned char kmask[2][KVB];
 };
-
-static constexpr float LOG2E = 1.4426950408889634f;
-static constexpr float LN2 = 0.6931471805599453f;
-
-template <class F>
-__device__ __attribute__((noinline)) void fwd_noinline_call(F&& f) { f(); }
 
 // ---------------------------------------------------------------------------
 // forward kernel
@@ -103,7 +68,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void attn_fwd_kernel(FwdParams p) {
     static_assert(D % 32 == 0);
     constexpr int DBLK = D / 32;     // 32-d output blocks
     constexpr int KSTEPS = D / 16;   // QK^T k-steps
-    constexpr int KVBLK = fwd_kvblk<D>();
+    constexpr int KVBLK = kvblk(D);
     constexpr int NBLK = KVBLK / 32;
 
     __shared__ FwdLds<D> lds;
@@ -140,7 +105,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void attn_fwd_kernel(FwdParams p) {
             #include "attn_fwd_body.inc"
             #undef FWD_EXIT
         };
-        fwd_noinline_call(fwd_body);
+        noinline_call(fwd_body);
     } else if constexpr (D == 128) {
         // d128-plain prefers the directly-called lambda with a VALUE copy of
         // the params (measured fwd-only 498 vs 424 TF): the copy frees the
@@ -249,7 +214,7 @@ void launch_attn_fwd(const FwdParams& p, int head_dim, hipStream_t stream) {
     if (v2env && v2env[0] == '1') {
         if (launch_attn_fwd_v2(p, head_dim, stream)) return;
     }
-    long qtiles = (p.nq + QROWS_WG - 1) / QROWS_WG;
+    long qtiles = ceil_div(p.nq, QROWS_WG);
     dim3 grid(p.paired ? (qtiles + 1) / 2 : qtiles, p.b * p.h,
               p.kv_split > 1 ? p.kv_split : 1);
     dim3 block(NTHREADS);

@@ -1,6 +1,6 @@
 // forward-kernel per-q-tile body — textually included TWICE by
 // attn_fwd.hip (preprocessor include, not a header):
-//   * PAIRED instantiations: inside a lambda passed to fwd_noinline_call —
+//   * PAIRED instantiations: inside a lambda passed to noinline_call —
 //     the noinline frame confines register allocation to the body (the pair
 //     loop's liveness otherwise spills 532 B/lane; measured +5% causal)
 //   * plain instantiations: directly at pit-loop scope — the SAME body via
@@ -47,34 +47,18 @@
 
     // ---- causal / lookback tile bounds for this workgroup: the masked
     // region is contiguous, so the tile range is computed once (keeps the
-    // staging pipeline branch-free)
-    // q positions in kv-local coordinates: qpos(i) = i * q_stride + diag
+    // staging pipeline branch-free).  The algebra lives in attn_mask.h; q
+    // positions are in kv-local coordinates.
+    const Mask M = mask_of(P);
     const long wg_i_min = (long)qtile * QROWS_WG;
     const long wg_i_max = min((long)(qtile + 1) * QROWS_WG, P.nq) - 1;
-    const long wg_q_min = wg_i_min * P.q_stride + P.diag;
-    const long wg_q_max = wg_i_max * P.q_stride + P.diag;
-    const long qpos_i = i * P.q_stride + P.diag;      // this lane's q position
-    const int num_kv_tiles = (int)((P.nk + KVBLK - 1) / KVBLK);
-
-    int t_lo = 0, t_hi = num_kv_tiles;
-    if (P.causal) {
-        t_hi = wg_q_max < 0 ? 0 : min((long)num_kv_tiles, wg_q_max / KVBLK + 1);
-    }
-    if (P.has_win) {
-        // tile t attends iff j0 + KVBLK - 1 >= wg_q_min - win
-        long x = wg_q_min - P.win - KVBLK + 1;
-        t_lo = x <= 0 ? 0 : (int)((x + KVBLK - 1) / KVBLK);
-        if (t_lo > t_hi) t_lo = t_hi;
-    }
-    if (split_mode) {
-        // this z's share of THIS WG's valid tile range (fractional split:
-        // a global-range split is skewed against the causal trapezoid)
-        int valid = t_hi - t_lo;
-        int per_split = (valid + P.kv_split - 1) / P.kv_split;
-        int base = t_lo;
-        t_lo = base + min(valid, zsplit * per_split);
-        t_hi = base + min(valid, (zsplit + 1) * per_split);
-    }
+    const long wg_q_min = M.qpos(wg_i_min);
+    const long wg_q_max = M.qpos(wg_i_max);
+    const long qpos_i = M.qpos(i);                    // this lane's q position
+    TileRange tr = M.kv_tile_range(wg_i_min, wg_i_max, P.nk, KVBLK);
+    // this z's share of THIS WG's valid tile range
+    if (split_mode) tr = split_share(tr, P.kv_split, zsplit);
+    const int t_lo = tr.lo, t_hi = tr.hi;
 
     // ---- T14 async-stage split: per-thread staging registers
     constexpr int CH_PER_ROW = D * 2 / 16;
@@ -180,8 +164,7 @@
         const long jmax = min(j0 + KVBLK, P.nk) - 1;
         const bool full_tile =
             (jmax - j0 == KVBLK - 1) &&
-            (!P.causal || jmax <= wg_q_min) &&
-            (!P.has_win || (wg_q_max - j0) <= P.win) &&
+            M.uncut(wg_q_min, wg_q_max, j0, jmax) &&
             !P.kmask && !P.bias;
 
         __syncthreads();
@@ -288,8 +271,7 @@
                             : ((long)b * P.h + h) * P.nk + j;
                         x += P.bias[bi] * LOG2E;
                     }
-                    if (P.causal) ok = ok && (j <= qpos_i);
-                    if (P.has_win) ok = ok && (qpos_i - j <= P.win);
+                    ok = M.attends(qpos_i, j, ok);
                     if (P.kmask) ok = ok && lds.kmask[par][j - j0];
                     if (!ok) x = MASK_VALUE_F;
                     s[kb][r] = x;

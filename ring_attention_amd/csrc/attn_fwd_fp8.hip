@@ -47,25 +47,11 @@ typedef int i32x8_ __attribute__((ext_vector_type(8)));
 
 static constexpr int FP8_WAVES = 8;
 static constexpr int FP8_QROWS_WAVE = 32;
-static constexpr int FP8_QROWS_WG = FP8_WAVES * FP8_QROWS_WAVE;   // 256
+static constexpr int FP8_QROWS_WG = ROWS_WG;                      // 256
+static_assert(FP8_QROWS_WG == FP8_WAVES * FP8_QROWS_WAVE);
 static constexpr int FP8_NTHREADS = FP8_WAVES * 64;               // 512
-// KVBLK 256 measured NEGATIVE and wrong (profiles/README.md) — keep 128
-static constexpr int FP8_KVBLK = 128;
+// FP8_KVBLK (128) comes from attn_mask.h
 static constexpr int FP8_NBLK = FP8_KVBLK / 32;                   // 4
-
-// 16-byte-chunk XOR swizzle within a row (CH chunks per row), same
-// both-sides rule as the bf16 kernels
-template <int CH>
-__device__ __forceinline__ int fswz(int row, int chunk) {
-    return chunk ^ (row & (CH < 8 ? CH - 1 : 7));
-}
-
-__device__ __forceinline__ float fp8_cross_half(float x) {
-    union { float f; unsigned u; } c; c.f = x;
-    u32x2 r = __builtin_amdgcn_permlane32_swap(c.u, c.u, false, false);
-    union { unsigned u; float f; } lo, hi; lo.u = r[0]; hi.u = r[1];
-    return (threadIdx.x & 32) ? lo.f : hi.f;
-}
 
 template <int D>
 struct Fp8Lds {
@@ -74,17 +60,12 @@ struct Fp8Lds {
     unsigned char ks[2][FP8_KVBLK * (D / 64)];           // k (row, chunk) e8m0
 };
 
-template <class F>
-__device__ __attribute__((noinline)) void fp8_noinline_call(F&& f) { f(); }
-
 template <int D, bool PAIRED>
 __global__ __launch_bounds__(FP8_NTHREADS, 1)
 void attn_fwd_fp8_kernel(Fp8FwdParams p) {
     constexpr int DBLK = D / 32;
     constexpr int NDCH = D / 64;          // 64-deep MFMA k-chunks per head dim
     constexpr int KCH = D * 2 / 32;       // 16B LDS chunks per K row (D bytes)
-    constexpr float LOG2E_ = 1.4426950408889634f;
-    constexpr float LN2_ = 0.6931471805599453f;
 
     __shared__ Fp8Lds<D> lds;
 
@@ -133,12 +114,13 @@ void attn_fwd_fp8_kernel(Fp8FwdParams p) {
     #pragma unroll
     for (int db = 0; db < DBLK; ++db) o_acc[db] = f32x16{};
 
-    // ---- causal tile range for this workgroup
+    // ---- causal tile range for this workgroup (attn_mask.h): standard
+    // causal, qpos(i) = i, no window.  nq and nk are padded to whole tiles,
+    // so the walk covers the padded keys and masks them at nk_true below.
+    const Mask M{P.causal, 0, 0, 1, 0};
     const long wg_q_min = (long)qtile * FP8_QROWS_WG;
     const long wg_q_max = wg_q_min + FP8_QROWS_WG - 1;
-    const int num_kv_tiles = (int)(P.nk / FP8_KVBLK);
-    const int t_hi = P.causal
-        ? min(num_kv_tiles, (int)(wg_q_max / FP8_KVBLK) + 1) : num_kv_tiles;
+    const int t_hi = M.kv_tile_range(wg_q_min, wg_q_max, P.nk, FP8_KVBLK).hi;
 
     // ---- staging (one uint4 per thread per image per tile)
     const unsigned char* kbase = (const unsigned char*)P.k
@@ -177,18 +159,18 @@ void attn_fwd_fp8_kernel(Fp8FwdParams p) {
             {   // K: D-byte rows, KCH 16B chunks
                 int c = tid + r * FP8_NTHREADS;
                 int row = c / KCH, ch = c % KCH;
-                *(uint4*)(lds.k[par] + row * D + fswz<KCH>(row, ch) * 16) = kst[r];
+                *(uint4*)(lds.k[par] + row * D + swz<KCH>(row, ch) * 16) = kst[r];
             }
             {   // V^T: KVBLK-byte rows, VCH chunks
                 int c = tid + r * FP8_NTHREADS;
                 int row = c / VCH, ch = c % VCH;
-                *(uint4*)(lds.vt[par] + row * FP8_KVBLK + fswz<8>(row, ch) * 16) = vst[r];
+                *(uint4*)(lds.vt[par] + row * FP8_KVBLK + swz<8>(row, ch) * 16) = vst[r];
             }
         }
         if (tid < FP8_KVBLK * NDCH) lds.ks[par][tid] = ksst;
     };
 
-    const float scale2 = P.scale * LOG2E_;
+    const float scale2 = P.scale * LOG2E;
 
     if (t_hi > 0) {
         load_tile();
@@ -200,7 +182,7 @@ void attn_fwd_fp8_kernel(Fp8FwdParams p) {
         const int par = t & 1;
         const long j0 = (long)t * FP8_KVBLK;
         const bool full_tile = (j0 + FP8_KVBLK <= P.nk_true)
-            && (!P.causal || (j0 + FP8_KVBLK - 1 <= wg_q_min));
+            && M.uncut(wg_q_min, wg_q_max, j0, j0 + FP8_KVBLK - 1);
 
         __syncthreads();
 
@@ -216,9 +198,9 @@ void attn_fwd_fp8_kernel(Fp8FwdParams p) {
             for (int dc = 0; dc < NDCH; ++dc) {
                 union { i32x8_ v; uint4 u4[2]; } kf;
                 kf.u4[0] = *(const uint4*)(lds.k[par] + krow * D
-                               + fswz<KCH>(krow, 4 * dc + 2 * lhi) * 16);
+                               + swz<KCH>(krow, 4 * dc + 2 * lhi) * 16);
                 kf.u4[1] = *(const uint4*)(lds.k[par] + krow * D
-                               + fswz<KCH>(krow, 4 * dc + 2 * lhi + 1) * 16);
+                               + swz<KCH>(krow, 4 * dc + 2 * lhi + 1) * 16);
                 int sa = lds.ks[par][krow * NDCH + dc];
                 acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
                     kf.v, qf[dc].v, acc, 0, 0, 0, sa, 0, qs[dc]);
@@ -248,13 +230,13 @@ void attn_fwd_fp8_kernel(Fp8FwdParams p) {
                 for (int r = 0; r < 16; ++r) {
                     long j = j0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
                     float x = s[kb][r] * scale2;
-                    if (j >= P.nk_true) x = MASK_VALUE_F;   // padded keys
-                    if (P.causal && j > i) x = MASK_VALUE_F; // qpos(i) = i
+                    // padded keys, then the mask at qpos(i) = i
+                    if (!M.attends(i, j, j < P.nk_true)) x = MASK_VALUE_F;
                     s[kb][r] = x;
                     smax = fmaxf(smax, x);
                 }
         }
-        smax = fmaxf(smax, fp8_cross_half(smax));
+        smax = fmaxf(smax, cross_half(smax));
 
         float m_new = fmaxf(m_run, smax);
         const bool any_growth = !__all(smax <= m_run);
@@ -285,7 +267,7 @@ void attn_fwd_fp8_kernel(Fp8FwdParams p) {
             #pragma unroll
             for (int x2 = 0; x2 < w; ++x2) partial[x2] += partial[x2 + w];
         float rowsum = partial[0];
-        rowsum += fp8_cross_half(rowsum);
+        rowsum += cross_half(rowsum);
         if (any_growth) {
             float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
             l_run = l_run * alpha + rowsum;
@@ -324,9 +306,9 @@ void attn_fwd_fp8_kernel(Fp8FwdParams p) {
                 int drow = db * 32 + l31;
                 union { i32x8_ v; uint4 u4[2]; } vf;
                 vf.u4[0] = *(const uint4*)(lds.vt[par] + drow * FP8_KVBLK
-                                           + fswz<8>(drow, 4 * c + 2 * lhi) * 16);
+                                           + swz<8>(drow, 4 * c + 2 * lhi) * 16);
                 vf.u4[1] = *(const uint4*)(lds.vt[par] + drow * FP8_KVBLK
-                                           + fswz<8>(drow, 4 * c + 2 * lhi + 1) * 16);
+                                           + swz<8>(drow, 4 * c + 2 * lhi + 1) * 16);
                 int sv = ((const unsigned char*)P.vs)[
                     (((long)b * P.hk + hk) * D + drow) * P.nvs + (t * 2 + c)];
                 o_acc[db] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(
@@ -353,10 +335,10 @@ void attn_fwd_fp8_kernel(Fp8FwdParams p) {
         }
     if (lhi == 0) {
         float* lsep = P.lse + ((long)b * P.h + h) * P.nq;
-        lsep[i] = __logf(l_safe) + m_run * LN2_;
+        lsep[i] = __logf(l_safe) + m_run * LN2;
     }
     };
-    if constexpr (PAIRED) fp8_noinline_call(fp8_body);
+    if constexpr (PAIRED) noinline_call(fp8_body);
     else fp8_body();
     }  // pair loop
 }

@@ -54,24 +54,9 @@ static constexpr int NTHREADS = 256;
 static constexpr int QROWS_WAVE = 64;
 static constexpr int QROWS_WG = WAVES * QROWS_WAVE;   // 256
 
-static constexpr float LOG2E = 1.4426950408889634f;
-static constexpr float LN2 = 0.6931471805599453f;
-
 typedef unsigned long long u64_t;
 typedef __attribute__((address_space(3))) unsigned int lds_u32;
 typedef __attribute__((address_space(1))) unsigned int glb_u32;
-
-__device__ __forceinline__ float fast_tanhf(float x) {
-    float e = __builtin_amdgcn_exp2f(x * 2.885390081777927f);
-    return 1.f - 2.f * __builtin_amdgcn_rcpf(e + 1.f);
-}
-
-__device__ __forceinline__ float cross_half(float x) {
-    union { float f; unsigned u; } c; c.f = x;
-    u32x2 r = __builtin_amdgcn_permlane32_swap(c.u, c.u, false, false);
-    union { unsigned u; float f; } lo, hi; lo.u = r[0]; hi.u = r[1];
-    return (threadIdx.x & 32) ? lo.f : hi.f;
-}
 
 template <int KVB, int D>
 struct V2Lds {
@@ -180,7 +165,9 @@ __global__ __launch_bounds__(NTHREADS, 1) void attn_fwd_v2_kernel(FwdParams p) {
             asm volatile("" :: "a"(o_acc[qb][db]));
     }
 
-    // ---- tile bounds (same algebra as v1)
+    // ---- tile bounds: a PRIVATE copy of the attn_mask.h algebra, the only
+    // one left outside that header — no test runs this parked kernel, so a
+    // conversion could not be verified (docs/KERNELS.md, "Mask edges")
     const long wg_i_min = (long)qtile * QROWS_WG;
     const long wg_i_max = min((long)(qtile + 1) * QROWS_WG, p.nq) - 1;
     const long wg_q_min = wg_i_min * p.q_stride + p.diag;

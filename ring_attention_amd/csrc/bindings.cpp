@@ -97,7 +97,7 @@ void attn_fwd(
     // windows are already uniform; ticks index per tile)
     p.paired = 0;
     {
-        const long T = (Nq + 255) / 256;      // QROWS_WG
+        const long T = ceil_div(Nq, ROWS_WG);
         // pairing halves grid.x — only engage when the paired grid (times
         // any grid.z split) still fills the 256 CUs (measured: engaging
         // below that idles half the chip and loses)
@@ -249,14 +249,14 @@ void attn_bwd(
         }
     };
     if (run_dq) {
-        const long Tq = (Nq + 255) / 256;
+        const long Tq = ceil_div(Nq, ROWS_WG);
         set_desc(desc_dq);
         p.paired = (!p.desc && pair_ok && ((Tq + 1) / 2) * B * H * z >= 256)
                        ? (int)Tq : 0;
         launch_attn_bwd_dq(p, (int)D, at::hip::getCurrentHIPStream());
     }
     if (run_dkv) {
-        const long Tk = (Nk + 255) / 256;
+        const long Tk = ceil_div(Nk, ROWS_WG);
         set_desc(desc_dkv);
         p.paired = (!p.desc && pair_ok && ((Tk + 1) / 2) * B * HK * z >= 256)
                        ? (int)Tk : 0;
@@ -665,6 +665,40 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::arg("k_new"), py::arg("v_new"), py::arg("k_pages"),
             py::arg("v_pages"), py::arg("k_scales"), py::arg("v_scales"),
             py::arg("block_table"), py::arg("seq_lens"), py::arg("append_lens"));
+    // host access to attn_mask.h, the kernels' own mask geometry (no GPU
+    // needed): the descriptor builder takes its shapes and bounds from here,
+    // and the CPU tests hold it to a brute-force mask
+    using ring_attn::Mask;
+    using ring_attn::TileRange;
+    auto pair = [](TileRange r) { return std::make_pair(r.lo, r.hi); };
+    py::class_<Mask>(mod, "Mask", "mask geometry (csrc/attn_mask.h)")
+        .def(py::init([](bool causal, long diag, long q_stride, bool has_win, long win) {
+                 TORCH_CHECK(q_stride >= 1, "q_stride must be >= 1");
+                 return Mask{causal, has_win, diag, q_stride, win};
+             }), py::arg("causal"), py::arg("diag") = 0, py::arg("q_stride") = 1,
+             py::arg("has_win") = false, py::arg("win") = 0)
+        .def("qpos", &Mask::qpos)
+        .def("attends", &Mask::attends, py::arg("qpos"), py::arg("j"), py::arg("ok") = true)
+        .def("attends_matrix", [](const Mask& m, int64_t nq, int64_t nk) {
+                 auto a = at::empty({nq, nk}, at::kBool);   // [i][j] = attends(qpos(i), j)
+                 for (int64_t i = 0; i < nq; ++i)
+                     for (int64_t j = 0; j < nk; ++j)
+                         a.data_ptr<bool>()[i * nk + j] = m.attends(m.qpos(i), j);
+                 return a;
+             })
+        .def("uncut", &Mask::uncut, py::arg("q_lo"), py::arg("q_hi"), py::arg("j0"), py::arg("jmax"))
+        .def("kv_tile_range", [pair](const Mask& m, long i_min, long i_max, long nk, int w) {
+                 return pair(m.kv_tile_range(i_min, i_max, nk, w)); })
+        .def("q_tile_range", [pair](const Mask& m, long j0, long jmax, long nq, int w) {
+                 return pair(m.q_tile_range(j0, jmax, nq, w)); });
+    mod.def("mask_split_share", [pair](int lo, int hi, int splits, int z) {
+        return pair(ring_attn::split_share({lo, hi}, splits, z)); });
+    mod.def("mask_tile_shapes", [](int d) {   // tile shapes at head dim d
+        return py::dict(py::arg("rows_wg") = ring_attn::ROWS_WG,
+                        py::arg("kvblk") = ring_attn::kvblk(d),
+                        py::arg("dkv_qt") = ring_attn::DKV_QT,
+                        py::arg("fp8_kvblk") = ring_attn::FP8_KVBLK);
+    });
     mod.def("attn_delta", &ring_attn::attn_delta, "fused delta = rowsum(dO*O) preprocess");
     mod.def("rotary_apply", &ring_attn::rotary_apply, "fused rotary embedding (table-driven)");
 }

@@ -167,35 +167,26 @@ def _walk_descriptors(kind, d, nq, nk, diag, q_stride, bh, device):
 
     Returns int32 (U, 3) [tile, t_lo, t_hi] — or None when the walk is
     empty.  `kind` "dq" = q-tiles (256 rows) walking kv tiles of the dq
-    kernel's KVBLK; "dkv" = kv-tiles walking q tiles of QT.  The bounds
-    replicate the kernels' causal tile math exactly (no window — desc mode
-    is only engaged without lookback).  Uniform unit work removes the
-    causal trapezoid imbalance at ANY grid size, with fp32-atomic
-    accumulation instead of pairing/splits.
+    kernel's KVBLK; "dkv" = kv-tiles walking q tiles of QT.  Shapes and
+    bounds ARE the kernels' own (csrc/attn_mask.h through the extension;
+    causal, no window — desc mode is only engaged without lookback).
+    Uniform unit work removes the causal trapezoid imbalance at ANY grid
+    size, with fp32-atomic accumulation instead of pairing/splits.
     """
     key = (kind, d, nq, nk, diag, q_stride, bh, str(device))
     hit = _DESC_CACHE.get(key)
     if hit is not None:
         return hit
+    ext = hip_ext.require()
+    shapes = ext.mask_tile_shapes(d)
+    mask = ext.Mask(True, diag, q_stride)
+    own = shapes["rows_wg"]
     if kind == "dq":
-        T = (nq + 255) // 256
-        W = 128 if d == 64 else 64          # dq_kvblk
-        n_w = (nk + W - 1) // W
-        bounds = []
-        for x in range(T):
-            imax = min((x + 1) * 256, nq) - 1
-            qmax = imax * q_stride + diag
-            hi = 0 if qmax < 0 else min(n_w, qmax // W + 1)
-            bounds.append((x, 0, hi))
+        n_own, n_walk, W, tile_range = nq, nk, shapes["kvblk"], mask.kv_tile_range
     else:
-        T = (nk + 255) // 256
-        W = 64                              # dkv QT (both head dims)
-        n_w = (nq + W - 1) // W
-        bounds = []
-        for x in range(T):
-            i_min = -(-(x * 256 - diag) // q_stride)   # ceil div
-            lo = 0 if i_min <= 0 else min(n_w, i_min // W)
-            bounds.append((x, lo, n_w))
+        n_own, n_walk, W, tile_range = nk, nq, shapes["dkv_qt"], mask.q_tile_range
+    bounds = [(x,) + tile_range(x * own, min((x + 1) * own, n_own) - 1, n_walk, W)
+              for x in range(-(-n_own // own))]
     total = sum(hi - lo for _, lo, hi in bounds)
     if total <= 0:
         desc = None

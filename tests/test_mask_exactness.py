@@ -3,8 +3,9 @@
 Every kernel reduces masking to a few integers (diag, q_stride, win, nk) plus
 a key-pad byte mask and turns them into a per-workgroup tile range, a
 `full_tile` predicate and a per-element `ok`; the forward, dq, dkv and fp8
-forward kernels each carry their own copy of that arithmetic, under the
-grid.z splits, PAIRED and the descriptor units.  The oracle comparisons on
+forward kernels take that arithmetic from csrc/attn_mask.h (checked here on
+the CPU against a brute-force mask) and apply it under the grid.z splits,
+PAIRED and the descriptor units.  The oracle comparisons on
 randn data are too loose to see one key too many among a hundred, so this
 file uses a COUNTING PROBE whose expected value depends only on which (i, j)
 pairs attend:
@@ -387,6 +388,58 @@ def test_walk_descriptors_cover_the_walk(geo, d, kind):
                 covered += [(x, t) for t in range(lo, hi)]
         assert len(covered) == len(set(covered)), "a pair is covered twice"
         assert needed <= set(covered), sorted(needed - set(covered))[:8]
+
+
+HEADER_CASES = [c + (w,) for c in CASES for w in _wins_of(c)]
+
+
+@pytest.mark.parametrize("walk", ["dq64", "dq128", "dkv64"])
+@pytest.mark.parametrize("case", HEADER_CASES,
+                         ids=lambda c: _case_id(c) + "_win{}".format(c[5]))
+def test_mask_header_against_brute_force(case, walk):
+    """csrc/attn_mask.h, reached through the extension's host functions,
+    against the brute-force mask: per owner tile (256 rows) of both walks
+    (dq: q rows walk kv tiles of 64 / 128; dkv: kv rows walk q tiles of 64)
+    the range covers every walked tile holding an attended pair, stays inside
+    [0, n_tiles] with lo <= hi, "uncut" holds only for tiles whose every
+    in-bounds pair attends, attends is the mask element for element, and the
+    grid.z shares are contiguous, ordered, disjoint and union to the range."""
+    ext = _ext()
+    nq, nk, diag, qs, causal, win = case
+    m = ext.Mask(causal, diag, qs, win is not None, 0 if win is None else win)
+    att = _attend(nq, nk, diag, qs, causal, win)
+    assert torch.equal(m.attends_matrix(nq, nk), att)
+    assert m.attends(m.qpos(nq - 1), nk - 1) == bool(att[-1, -1])
+    assert not m.attends(m.qpos(0), 0, False)      # the caller's own terms
+
+    own, W = 256, int(walk.lstrip("dqkv"))
+    shapes = ext.mask_tile_shapes(64 if W == 128 else 128)
+    assert shapes["rows_wg"] == own and W in (shapes["kvblk"], shapes["dkv_qt"])
+    if walk.startswith("dq"):
+        tile_range = m.kv_tile_range
+        uncut = lambda i0, i1, j0, j1: m.uncut(m.qpos(i0), m.qpos(i1), j0, j1)
+    else:
+        att = att.T
+        tile_range = m.q_tile_range
+        uncut = lambda j0, j1, i0, i1: m.uncut(m.qpos(i0), m.qpos(i1), j0, j1)
+    n_own, n_walk = att.shape
+    n_tiles = -(-n_walk // W)
+    for x in range(-(-n_own // own)):
+        o0, o1 = x * own, min((x + 1) * own, n_own) - 1
+        lo, hi = tile_range(o0, o1, n_walk, W)
+        assert 0 <= lo <= hi <= n_tiles, (x, lo, hi)
+        for t in range(n_tiles):
+            w0, w1 = t * W, min((t + 1) * W, n_walk) - 1
+            blk = att[o0:o1 + 1, w0:w1 + 1]
+            if blk.any():
+                assert lo <= t < hi, (x, t, lo, hi)
+            if uncut(o0, o1, w0, w1):
+                assert blk.all(), (x, t)
+        for splits in (1, 2, 3, 5):
+            shares = [ext.mask_split_share(lo, hi, splits, z) for z in range(splits)]
+            assert shares[0][0] == lo and shares[-1][1] == hi, (x, shares)
+            for (a0, a1), (b0, b1) in zip(shares, shares[1:]):
+                assert a0 <= a1 == b0 <= b1, (x, shares)
 
 
 # ---------------------------------------------------------------------------
