@@ -413,31 +413,56 @@ void attn_bwd_dkv_kernel(BwdParams p) {
 
     __shared__ DkvLds<D, QT> lds;
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wid = tid >> 6;
-    const int l31 = lane & 31;
-    const int lhi = lane >> 5;
-
-    const int bhk = blockIdx.y;
-    const int b = bhk / p.hk;
-    const int hkh = bhk % p.hk;
+    // the d64 body runs in a noinline frame (see the call below) and keeps
+    // its wave-uniform state in SGPRs: it captures nothing
+    constexpr bool FRAME = (D == 64);
+    // explicit LDS operand prefetch in the tile loop: d64 only (d128 has no
+    // registers for it, its tile loop already spills)
+    constexpr bool PREFETCH = (D == 64);
 
     // causal pairing (mirrored): kv-tile x attends T-x q-tiles, so WG x
     // runs kv-tiles (x, T-1-x) for uniform per-WG work
     const int n_pit = PAIRED
         ? (p.paired - 1 - (int)blockIdx.x == (int)blockIdx.x ? 1 : 2) : 1;
     for (int pit = 0; pit < n_pit; ++pit) {
-    const int kvtile = PAIRED
+    const int kvtile_wg = PAIRED
         ? (pit == 0 ? (int)blockIdx.x : p.paired - 1 - (int)blockIdx.x)
         : (p.desc ? p.desc[(long)blockIdx.x * 3] : (int)blockIdx.x);
     if (PAIRED && pit == 1) {
         __syncthreads();                       // LDS handoff between tiles
     }
 
-    auto dkv_body = [&]() {
-    const BwdParams P = p;   // register-local copy: the noinline frame would
-                             // otherwise re-read fields through scratch
+    auto dkv_body = [&](int kvtile_arg, unsigned long long kernarg) {
+    // FRAME: the parameters come by scalar loads from the kernarg segment and
+    // the workgroup / wave coordinates are re-derived here, so pointers, tile
+    // bounds, loop counters and mask integers are scalar and the tile loop's
+    // back-edge is a scalar branch.  Per-lane: tid, lane, l31, lhi and what derives from
+    // them (j, jc, col_valid, kmask_own).
+    const BwdParams P = [&] {
+        if constexpr (FRAME) {
+            BwdParams kp = kernarg_params<BwdParams>(kernarg);
+            kp.q = as_global(kp.q);         kp.k = as_global(kp.k);
+            kp.v = as_global(kp.v);         kp.dout = as_global(kp.dout);
+            kp.kmask = as_global(kp.kmask); kp.lse = as_global(kp.lse);
+            kp.delta = as_global(kp.delta); kp.dk = as_global(kp.dk);
+            kp.dv = as_global(kp.dv);       kp.dk_bf = as_global(kp.dk_bf);
+            kp.dv_bf = as_global(kp.dv_bf); kp.bias = as_global(kp.bias);
+            kp.desc = as_global(kp.desc);
+            return kp;
+        } else {
+            return p;            // register-local copy
+        }
+    }();
+    const int kvtile = uniform<FRAME>(kvtile_arg);
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wid = uniform<FRAME>(tid >> 6);
+    const int l31 = lane & 31;
+    const int lhi = lane >> 5;
+    const int bhk = blockIdx.y;
+    const int b = bhk / P.hk;
+    const int hkh = bhk % P.hk;
+
     const long j0_wg = (long)kvtile * ROWS_WG;
     const long jmax = min(j0_wg + ROWS_WG, P.nk) - 1;
     const long j = j0_wg + wid * KVROWS_WAVE + l31;
@@ -462,6 +487,14 @@ void attn_bwd_dkv_kernel(BwdParams p) {
 
     const Mask M = mask_of(P);
 
+    // K/V fragments land here, once (vmcnt(0), other counters untouched).
+    // Left in flight into the tile loop, the compiler's wait insertion sees
+    // them pending on the path around the loop prologue and guards the S/dP
+    // MFMAs, which read them, with counted vmcnt waits in EVERY iteration;
+    // in steady state those counts hold the MFMAs back for the q-tile
+    // global loads issued a few instructions earlier.
+    if constexpr (FRAME) __builtin_amdgcn_s_waitcnt(0x0F70);
+
     for (int g = 0; g < P.group; ++g) {
         // group boundary barrier: the previous group's last tile is still
         // being read from LDS by slower waves when this group's prologue
@@ -479,7 +512,8 @@ void attn_bwd_dkv_kernel(BwdParams p) {
         TileRange tr = M.q_tile_range(j0_wg, jmax, P.nq, QT);
         if (P.split > 1) tr = split_share(tr, P.split, (int)blockIdx.z);
         if (!PAIRED && P.desc)     // descriptor mode: exact unit bounds
-            tr = {P.desc[(long)blockIdx.x * 3 + 1], P.desc[(long)blockIdx.x * 3 + 2]};
+            tr = {uniform<FRAME>(P.desc[(long)blockIdx.x * 3 + 1]),
+                  uniform<FRAME>(P.desc[(long)blockIdx.x * 3 + 2])};
         const int t0 = tr.lo, t1 = tr.hi;
 
         // ---- T14 pipeline: per-thread staging registers
@@ -493,21 +527,40 @@ void attn_bwd_dkv_kernel(BwdParams p) {
         float lse_st = 0.f, delta_st = 0.f;
         long t_next = t0;
 
-        auto load_qtile = [&]() {
+        // Global loads of a q tile.  Addresses are a scalar tile base plus a
+        // 32-bit per-lane BYTE offset (the saddr + voffset form: one VGPR per
+        // access pattern, not a 64-bit pointer per access).  Every load is
+        // unconditional: a row past the end of a ragged last tile reads the
+        // tile's last valid row instead and is zeroed when the tile is
+        // written to LDS (write_qtile).  A `valid ? load : 0` here puts a
+        // zero write to the staging register in front of each load, and that
+        // write waits for EVERY global load in flight, once per tile, in
+        // the tile loop; likewise the lse product waits for its own load, so
+        // it is taken at write time too.
+        const unsigned qrow_bytes = (unsigned)(P.h * D) * 2u;
+        auto ld16 = [](const __bf16* base, unsigned boff) {
+            return *(const uint4*)((const char*)base + boff);
+        };
+        auto ld8h = [](const __bf16* base, unsigned boff) {
+            return *(const bf16x8*)((const char*)base + boff);
+        };
+        auto tile_rows = [&](long tile) {                      // valid q rows
+            return (int)(min((tile + 1) * QT, P.nq) - tile * QT);
+        };
+        auto load_qtile = [&](int tid) {
             const long i0 = t_next * QT;
-            const long imax_ = min(i0 + QT, P.nq) - 1;
-            const bool full = imax_ - i0 == QT - 1;
+            const int last = tile_rows(t_next) - 1;
+            const __bf16* qtile = qg + i0 * P.h * D;
+            const __bf16* dotile = dog + i0 * P.h * D;
             #pragma unroll
             for (int r = 0; r < QREGS; ++r) {
                 int c = tid + r * 512;
                 if (c < QCHUNKS) {
-                    long gr = i0 + c / CH;
+                    int lr = min(c / CH, last);
                     int ch = c % CH;
-                    const __bf16* src = qg + gr * P.h * D + ch * 8;
-                    const __bf16* srd = dog + gr * P.h * D + ch * 8;
-                    bool okr = full || gr <= imax_;
-                    qst[r] = okr ? *(const uint4*)src : uint4{0, 0, 0, 0};
-                    dost[r] = okr ? *(const uint4*)srd : uint4{0, 0, 0, 0};
+                    unsigned off = (unsigned)lr * qrow_bytes + ch * 16;
+                    qst[r] = ld16(qtile, off);
+                    dost[r] = ld16(dotile, off);
                 }
             }
             #pragma unroll
@@ -516,29 +569,39 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                 if (c < TPAIRS) {
                     int jp = c % (QT / 2);
                     int d0 = (c / (QT / 2)) * 8;
-                    long ra = i0 + jp * 2;
-                    bool oka = full || ra <= imax_;
-                    bool okb = full || ra + 1 <= imax_;
-                    const __bf16* qa_ = qg + ra * P.h * D + d0;
-                    const __bf16* da_ = dog + ra * P.h * D + d0;
-                    qtv_a[r] = oka ? *(const bf16x8*)qa_ : bf16x8{};
-                    qtv_b[r] = okb ? *(const bf16x8*)(qa_ + P.h * D) : bf16x8{};
-                    dov_a[r] = oka ? *(const bf16x8*)da_ : bf16x8{};
-                    dov_b[r] = okb ? *(const bf16x8*)(da_ + P.h * D) : bf16x8{};
+                    unsigned offa = (unsigned)min(jp * 2, last) * qrow_bytes + d0 * 2;
+                    unsigned offb = (unsigned)min(jp * 2 + 1, last) * qrow_bytes + d0 * 2;
+                    qtv_a[r] = ld8h(qtile, offa);
+                    qtv_b[r] = ld8h(qtile, offb);
+                    dov_a[r] = ld8h(dotile, offa);
+                    dov_b[r] = ld8h(dotile, offb);
                 }
             }
             if (tid < QT) {
-                long gi = i0 + tid;
-                bool okl = gi <= imax_;
-                // exp2-domain lse: one product per q row here, not one per
-                // lane per element in the hot loop (same fp32 product)
-                lse_st = okl ? lse_row[gi] * LOG2E : 0.f;
-                delta_st = okl ? delta_row[gi] : 0.f;
+                long gi = i0 + min(tid, last);
+                lse_st = lse_row[gi];
+                delta_st = delta_row[gi];
             }
             ++t_next;
         };
 
-        auto write_qtile = [&](int par) {
+        // `tile` is the q tile held in the staging registers
+        auto write_qtile = [&](int par, int tid, long tile) {
+            const int rows = tile_rows(tile);
+            if (rows < QT) {       // ragged last tile: rows past the end are 0
+                #pragma unroll
+                for (int r = 0; r < QREGS; ++r)
+                    if ((tid + r * 512) / CH >= rows) {
+                        qst[r] = uint4{0, 0, 0, 0};
+                        dost[r] = uint4{0, 0, 0, 0};
+                    }
+                #pragma unroll
+                for (int r = 0; r < TREGS; ++r) {
+                    int la = ((tid + r * 512) % (QT / 2)) * 2;
+                    if (la >= rows) { qtv_a[r] = bf16x8{}; dov_a[r] = bf16x8{}; }
+                    if (la + 1 >= rows) { qtv_b[r] = bf16x8{}; dov_b[r] = bf16x8{}; }
+                }
+            }
             #pragma unroll
             for (int r = 0; r < QREGS; ++r) {
                 int c = tid + r * 512;
@@ -556,27 +619,40 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                     // packed p/ds pairs are then the fragments as they stand
                     int jp = kperm_pair(c % (QT / 2));
                     int d0 = (c / (QT / 2)) * 8;
+                    // element (d0 + e, pair jp) sits at byte
+                    //   (d0 + e) * QT * 2 + ((jp * 4) ^ (((d0 + e) & TM) << 4))
+                    // of image `par`.  d0 % 8 == 0, so the swizzle term is
+                    // (e & TM) << 4; it is below the QT * 2 row size and the
+                    // buffer and row-group offsets have those bits clear, so
+                    // the XOR applies to the whole address: one base
+                    // register and one v_xor per store instead of eight
+                    // loop-invariant addresses held (and spilled) across
+                    // the tile loop
+                    static_assert((TM << 4) < QT * 2 && (D * QT * 2) % (QT * 2) == 0);
+                    const unsigned base = par * (D * QT * 2) + d0 * QT * 2 + jp * 4;
                     #pragma unroll
                     for (int e = 0; e < 8; ++e) {
-                        int dd = d0 + e;
-                        int byte_off = dd * QT * 2 + ((jp * 4) ^ ((dd & TM) << 4));
+                        unsigned byte_off = (base ^ ((e & TM) << 4)) + e * QT * 2;
                         __bf16 pq[2] = {qtv_a[r][e], qtv_b[r][e]};
                         __bf16 pd[2] = {dov_a[r][e], dov_b[r][e]};
-                        *(uint32_t*)((char*)lds.qt[par] + byte_off) = *(uint32_t*)pq;
-                        *(uint32_t*)((char*)lds.dot[par] + byte_off) = *(uint32_t*)pd;
+                        *(uint32_t*)((char*)lds.qt[0] + byte_off) = *(uint32_t*)pq;
+                        *(uint32_t*)((char*)lds.dot[0] + byte_off) = *(uint32_t*)pd;
                     }
                 }
             }
             if (tid < QT) {
-                lds.lse[par][tid] = lse_st;
-                lds.delta[par][tid] = delta_st;
+                const bool okl = tid < rows;
+                // exp2-domain lse: one product per q row here, not one per
+                // lane per element in the hot loop (same fp32 product)
+                lds.lse[par][tid] = okl ? lse_st * LOG2E : 0.f;
+                lds.delta[par][tid] = okl ? delta_st : 0.f;
             }
         };
 
         if (t0 < t1) {
-            load_qtile();
-            write_qtile(t0 & 1);
-            if (t0 + 1 < t1) load_qtile();
+            load_qtile(tid);
+            write_qtile(t0 & 1, tid, t0);
+            if (t0 + 1 < t1) load_qtile(tid);
         }
 
         for (int t = t0; t < t1; ++t) {
@@ -588,23 +664,87 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                 M.uncut(M.qpos(i0), M.qpos(imax), j0_wg, jmax) &&
                 !P.kmask;
 
+            // MFMA operand fragments of one 32-row q block: the S/dP pair
+            // (rows of the q / dO images) and the dv/dk pair (rows of the
+            // transposed images)
+            bf16x8 qa[KSTEPS], da[KSTEPS], doa[2 * DBLK], qta[2 * DBLK];
+            auto read_sdp = [&](int qb) {
+                #pragma unroll
+                for (int ks = 0; ks < KSTEPS; ++ks) {
+                    int qrow = qb * 32 + l31;
+                    int chunk = ks * 2 + lhi;
+                    qa[ks] = *(const bf16x8*)(lds.q[par] + qrow * D + swz<D / 8>(qrow, chunk) * 8);
+                    da[ks] = *(const bf16x8*)(lds.do_[par] + qrow * D + swz<D / 8>(qrow, chunk) * 8);
+                }
+            };
+            auto read_dvdk = [&](int qb) {
+                #pragma unroll
+                for (int db = 0; db < DBLK; ++db)
+                    #pragma unroll
+                    for (int half = 0; half < 2; ++half) {
+                        int qk = qb * 2 + half;
+                        int drow = db * 32 + l31;
+                        int ch = qk * 2 + lhi;
+                        doa[db * 2 + half] = *(const bf16x8*)(lds.dot[par] + drow * QT +
+                                                              ((ch ^ (drow & TM))) * 8);
+                        qta[db * 2 + half] = *(const bf16x8*)(lds.qt[par] + drow * QT +
+                                                              ((ch ^ (drow & TM))) * 8);
+                    }
+            };
+
+            // masked path: the lane's half offset and its one 64-bit q
+            // position per tile.  Both are made opaque: left visible, the
+            // per-register terms are folded back into 32 loop-invariant
+            // per-lane products that live in scratch
+            const int rows_m1 = (int)(imax - i0);            // last valid tile row
+            int lhi4 = 4 * lhi;
+            asm volatile("" : "+v"(lhi4));
+            long qp_lane = M.qpos(i0 + lhi4);
+            asm volatile("" : "+v"(qp_lane));
+
             __syncthreads();
 
-            if (t + 1 < t1) write_qtile(par ^ 1);
-            if (t + 2 < t1) load_qtile();
+            // PREFETCH: each batch of LDS reads is issued one block of work
+            // ahead of the MFMAs that consume it, and pinned there (the
+            // scheduler otherwise sinks every read to just above its MFMA,
+            // where both waves of the SIMD wait out the round trip together):
+            //   barrier | S/dP reads of q block 0 | staging of tile t+1
+            //   per q block: S/dP MFMAs | dv/dk reads | softmax, ds
+            //              | S/dP reads of the next q block | dv/dk MFMAs
+            // Nothing is read from image `par` ahead of the barrier above.
+            if constexpr (PREFETCH) {
+                read_sdp(0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+
+            // the staging addresses are a few VALU ops from tid.  Left
+            // loop-invariant they are hoisted, spilled under the loop's
+            // register pressure and reloaded from scratch just ahead of
+            // their use, one exposed memory round trip each per tile; the
+            // empty asm makes tid opaque so they are rebuilt in the loop
+            int tid_l = tid;
+            if constexpr (FRAME) asm volatile("" : "+v"(tid_l));
+            if (t + 1 < t1) write_qtile(par ^ 1, tid_l, t + 1);
+            if (t + 2 < t1) load_qtile(tid_l);
 
             #pragma unroll
             for (int qb = 0; qb < QBLKS; ++qb) {
                 // S2[q][kv], dP[q][kv]: lane = kv, q rows in regs
                 f32x16 s2 = f32x16{}, dp = f32x16{};
+                if constexpr (!PREFETCH) read_sdp(qb);
                 #pragma unroll
                 for (int ks = 0; ks < KSTEPS; ++ks) {
-                    int qrow = qb * 32 + l31;
-                    int chunk = ks * 2 + lhi;
-                    bf16x8 qa = *(const bf16x8*)(lds.q[par] + qrow * D + swz<D / 8>(qrow, chunk) * 8);
-                    bf16x8 da = *(const bf16x8*)(lds.do_[par] + qrow * D + swz<D / 8>(qrow, chunk) * 8);
-                    s2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa, kf[ks], s2, 0, 0, 0);
-                    dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da, vf[ks], dp, 0, 0, 0);
+                    s2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa[ks], kf[ks], s2, 0, 0, 0);
+                    dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(da[ks], vf[ks], dp, 0, 0, 0);
+                }
+                // the first row group's lse / delta go ahead of the dv/dk
+                // batch: the softmax block starts on them
+                f32x4 lse_g0 = f32x4{}, delta_g0 = f32x4{};
+                if constexpr (PREFETCH) {
+                    lse_g0 = *(const f32x4*)(lds.lse[par] + qb * 32 + 4 * lhi);
+                    delta_g0 = *(const f32x4*)(lds.delta[par] + qb * 32 + 4 * lhi);
+                    read_dvdk(qb);
+                    __builtin_amdgcn_sched_barrier(0);
                 }
 
                 alignas(16) uint32_t p_pk[8], ds_pk[8];
@@ -615,7 +755,10 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                         // per-group wide loads (8 live regs, not 32): regs
                         // 4g..4g+3 are consecutive qloc -> one b128 each
                         f32x4 lse4, delta4;
-                        {
+                        if (PREFETCH && (x2 >> 1) == 0) {
+                            lse4 = lse_g0;
+                            delta4 = delta_g0;
+                        } else {
                             int base = qb * 32 + 8 * (x2 >> 1) + 4 * lhi;
                             lse4 = *(const f32x4*)(lds.lse[par] + base);
                             delta4 = *(const f32x4*)(lds.delta[par] + base);
@@ -649,7 +792,10 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                         // per-group wide loads (8 live regs, not 32): regs
                         // 4g..4g+3 are consecutive qloc -> one b128 each
                         f32x4 lse4, delta4;
-                        {
+                        if (PREFETCH && (x2 >> 1) == 0) {
+                            lse4 = lse_g0;
+                            delta4 = delta_g0;
+                        } else {
                             int base = qb * 32 + 8 * (x2 >> 1) + 4 * lhi;
                             lse4 = *(const f32x4*)(lds.lse[par] + base);
                             delta4 = *(const f32x4*)(lds.delta[par] + base);
@@ -657,8 +803,16 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                         #pragma unroll
                         for (int e = 0; e < 2; ++e) {
                             int r = 2 * x2 + e;
-                            int qloc = qb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
-                            long i = i0 + qloc;
+                            // q row of register r: a compile-time row cr of
+                            // the tile plus the lane's half offset.  The
+                            // row test is 32-bit against the tile's row
+                            // count and qpos(i) is the lane's one 64-bit
+                            // base plus the SCALAR cr * q_stride: the same
+                            // integers as qpos(i0 + qloc), without 32
+                            // per-lane 64-bit products held (spilled)
+                            // across the tile loop
+                            const int cr = qb * 32 + (r & 3) + 8 * (r >> 2);
+                            const int qloc = cr + lhi4;
                             float x, dtanh = 1.f;
                             if constexpr (SOFTCLAMP) {
                                 float inv_v = __builtin_amdgcn_rcpf(P.softclamp_value);
@@ -668,16 +822,17 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                             } else {
                                 x = s2[r] * scale2;
                             }
-                            bool ok = col_valid && i <= imax;
+                            bool ok = col_valid && qloc <= rows_m1;
                             if constexpr (BIAS) {
                                 if (ok) {
+                                    const long i = i0 + qloc;
                                     const long bi = P.bias_mat
                                         ? (((long)b * P.h + h) * P.nq + i) * P.nk + j
                                         : ((long)b * P.h + h) * P.nk + j;
                                     x += P.bias[bi] * LOG2E;
                                 }
                             }
-                            ok = M.attends(M.qpos(i), j, ok);
+                            ok = M.attends(qp_lane + (long)cr * M.q_stride, j, ok);
                             if (P.kmask) ok = ok && kmask_own;
                             float pv = ok ? __builtin_amdgcn_exp2f(x - lse4[r & 3]) : 0.f;
                             pe[e] = pv;
@@ -694,21 +849,22 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                 // fragments of k-step `half` as packed: q rows
                 // 16*half + 4*lhi + {0,1,2,3,8,9,10,11}, the order the
                 // qt/dot images are staged in (kperm_pair)
+                if constexpr (PREFETCH) {
+                    if (qb + 1 < QBLKS) {
+                        read_sdp(qb + 1);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                } else {
+                    read_dvdk(qb);
+                }
                 #pragma unroll
                 for (int db = 0; db < DBLK; ++db)
                     #pragma unroll
                     for (int half = 0; half < 2; ++half) {
-                        int qk = qb * 2 + half;
-                        int drow = db * 32 + l31;
-                        int ch = qk * 2 + lhi;
-                        bf16x8 doa = *(const bf16x8*)(lds.dot[par] + drow * QT +
-                                                      ((ch ^ (drow & TM))) * 8);
                         dv_acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                            doa, *(const bf16x8*)(p_pk + 4 * half), dv_acc[db], 0, 0, 0);
-                        bf16x8 qta = *(const bf16x8*)(lds.qt[par] + drow * QT +
-                                                      ((ch ^ (drow & TM))) * 8);
+                            doa[db * 2 + half], *(const bf16x8*)(p_pk + 4 * half), dv_acc[db], 0, 0, 0);
                         dk_acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                            *(const bf16x8*)(ds_pk + 4 * half), qta, dk_acc[db], 0, 0, 0);
+                            *(const bf16x8*)(ds_pk + 4 * half), qta[db * 2 + half], dk_acc[db], 0, 0, 0);
                     }
             }
         }
@@ -812,8 +968,8 @@ void attn_bwd_dkv_kernel(BwdParams p) {
     // (measured headline +4%, causal +17-24%); d128 is better DIRECT for
     // both forms (paired: 125 -> 138 TF causal 8k — the same value-copy
     // preference as the d128 fwd/dq bodies), so only d64 takes the call
-    if constexpr (D == 64) noinline_call(dkv_body);
-    else dkv_body();
+    if constexpr (FRAME) noinline_call(dkv_body, kvtile_wg, kernarg_address());
+    else dkv_body(kvtile_wg, 0ull);
     }  // pair loop
 }
 

@@ -78,6 +78,66 @@ __device__ __forceinline__ float cross_half(float x) {
 template <class F>
 __device__ __attribute__((noinline)) void noinline_call(F&& f) { f(); }
 
+// The same frame for a body that captures nothing.  A lambda called through a
+// noinline frame reads everything it captures by reference back from memory
+// into VGPRs, and the compiler then treats values that are the same in every
+// lane as per-lane: loop bounds, pointers and mask integers become 64-bit
+// VALU compares and exec-masked branches.  Such a body instead takes its one
+// varying scalar and the address of the kernel's parameters as arguments,
+// re-derives the rest from blockIdx / threadIdx and reads the parameters with
+// kernarg_params().
+// not_tail_called: a call that passes no pointer into the caller's frame gets
+// the IR `tail` marker, and a function with such a call site loses the
+// local-function exemption from saving callee-saved registers — the frame
+// would open and close with ~110 scratch stores and loads.
+template <class F>
+__device__ __attribute__((noinline, not_tail_called))
+void noinline_call(F&& f, int x, unsigned long long kernarg) { f(x, kernarg); }
+
+// wave-uniform value -> SGPR (the caller vouches that every lane holds x)
+template <bool ON>
+__device__ __forceinline__ int uniform(int x) {
+    if constexpr (ON) return __builtin_amdgcn_readfirstlane(x);
+    else return x;
+}
+
+// Address of the kernarg segment.  KERNELS ONLY: in a called function the
+// builtin is lowered to a null pointer, so the kernel takes the address and
+// hands it to the frame.
+__device__ __forceinline__ unsigned long long kernarg_address() {
+    return (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
+}
+
+// The kernel's parameter struct, read from the kernarg segment at `kernarg`
+// (kernarg_address() of a kernel whose ONLY parameter is a T by value).  The
+// address goes through readfirstlane and the loads through the constant
+// address space, so they are scalar loads and every field arrives
+// wave-uniform in SGPRs.
+template <class T>
+__device__ __forceinline__ T kernarg_params(unsigned long long kernarg) {
+    static_assert(sizeof(T) % 4 == 0);
+    typedef const __attribute__((address_space(4))) unsigned int* const_words;
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)kernarg);
+    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(kernarg >> 32));
+    const_words src = (const_words)(((unsigned long long)hi << 32) | lo);
+    union { T t; unsigned w[sizeof(T) / 4]; } u;
+    #pragma unroll
+    for (unsigned i = 0; i < sizeof(T) / 4; ++i) u.w[i] = src[i];
+    return u.t;
+}
+
+// A pointer rebuilt from kernarg words has no address space the compiler can
+// see, and is accessed with flat instructions; those also count on lgkmcnt,
+// the counter the LDS operand waits are counted on.  Kernel parameters point
+// to global memory (or are null): rebuilding p as a global-address-space
+// pointer says so, and the compiler carries it to every access derived from
+// p.  (Through the integer: a direct generic -> global -> generic pointer
+// cast pair is folded away.)
+template <class T>
+__device__ __forceinline__ T* as_global(T* p) {
+    return (T*)(__attribute__((address_space(1))) T*)(unsigned long long)p;
+}
+
 static constexpr float LOG2E = 1.4426950408889634f;
 static constexpr float LN2 = 0.6931471805599453f;
 #endif
