@@ -18,6 +18,9 @@ falls back to the eager partial so this example runs anywhere.
 length, and each step appends the new token's K/V to the tail rank's pages
 before decoding — the cache grows page by page, nothing is reallocated.
 Works with and without `--fp8` (fused quantising append), on GPU and CPU.
+In a single process the ragged prompts first go through `paged_prefill_attn`
+right after the prompt append: causal attention straight off the pages, one
+length and one diagonal per sequence.
 """
 
 from __future__ import annotations
@@ -146,6 +149,23 @@ def serve_paged(args, rank, world, device, dtype):
                          fp8=args.fp8, device=device)
     cache.append(k_loc, v_loc, local)          # ragged prompt prefill
     del k_loc, v_loc
+
+    if world == 1:
+        # the prompt's own attention, straight off the pages it was just
+        # appended to (append first, then attend): ragged, causal, no dense
+        # K/V copy.  Stand-in queries; in a real server they come from the
+        # model, layer by layer.
+        from ring_attention_amd import paged_prefill_attn
+        torch.manual_seed(11)
+        q_prompt = torch.randn(b, t, h, d, device=device, dtype=dtype)
+        t0 = time.perf_counter()
+        o_prompt = paged_prefill_attn(q_prompt, cache, local, causal=True)
+        if device == "cuda":
+            torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        print(f"paged prefill  prompts {local[0]}..{local[-1]}  {dt*1e3:.2f} ms  "
+              f"out[0,-1,0,:4] = {o_prompt[0, local[0] - 1, 0, :4].float().tolist()}")
+        del q_prompt, o_prompt
 
     torch.manual_seed(7)
     q = torch.randn(b, h, 1, d, device=device, dtype=dtype)

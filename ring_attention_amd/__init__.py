@@ -20,6 +20,7 @@ from .models import (
     apply_rotary_pos_emb,
 )
 from .paged_cache import PagedKVCache
+from .paged_prefill import paged_prefill_attn
 from .tree_decode import (
     tree_attn_decode,
     tree_attn_decode_fp8,
@@ -51,6 +52,7 @@ __all__ = [
     "tree_attn_decode_fp8",
     "tree_attn_decode_paged",
     "PagedKVCache",
+    "paged_prefill_attn",
     "zig_zag_attn",
     "zig_zag_pad_seq",
     "zig_zag_shard",

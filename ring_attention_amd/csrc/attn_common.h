@@ -357,6 +357,38 @@ struct PagedAppendParams {
 void launch_paged_kv_append(const PagedAppendParams& p, int head_dim, bool fp8,
                             hipStream_t stream);
 
+// Paged prefill (attn_fwd_paged.hip): the dense forward over pool pages with
+// per-sequence geometry.  Query t < q_lens[b] sits at position
+// seq_lens[b] - q_lens[b] + t (its tokens are already cached) and attends
+// keys [0, seq_lens[b]) under Mask{causal, has_win, diag = seq_len - q_len,
+// q_stride = 1, win}.
+struct PagedPrefillParams {
+    const void* q;          // bf16 (B, T, H, D)
+    const void* k_pages;    // bf16 or e4m3 bytes (P, HK, PS, D)
+    const void* v_pages;
+    const void* kscale;     // fp8 mode: e8m0 per row (P, HK, PS)
+    const void* vscale;
+    const int* block_table; // int32 (B, max_pages); entries at or beyond
+                            // ceil(seq_len / PS) are never read
+    const int* seq_lens;    // int32 (B)
+    const int* q_lens;      // int32 (B): 0 <= q_lens[b] <= min(T, seq_lens[b])
+    float* o_part;          // kv_split > 1: fp32 (S, B, H, D, T) partials
+    float* m_part;          // fp32 (S, B, H, T)
+    float* l_part;          // fp32 (S, B, H, T)
+    void* out;              // kv_split <= 1: bf16 (B, T, H, D)
+    float* lse;             // fp32 (B, H, T)
+    int b, h, hk;
+    int t;                  // T: q rows per sequence in the buffers
+    int page_shift, max_pages, num_pages;
+    int causal, has_win;
+    long win;
+    float scale;
+    int kv_split;           // grid.z shares of each workgroup's own tile range
+};
+
+void launch_attn_fwd_paged(const PagedPrefillParams& p, int head_dim, bool fp8,
+                           hipStream_t stream);
+
 struct Fp8FwdParams {
     const void* q;      // e4m3 bytes (B, Nq, H, D)
     const void* k;      // e4m3 bytes (B, Nk, H, D)

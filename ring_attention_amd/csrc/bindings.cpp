@@ -597,6 +597,69 @@ void paged_kv_append(
     TORCH_CHECK(hipGetLastError() == hipSuccess, "paged append launch failed");
 }
 
+void attn_fwd_paged(
+    at::Tensor q, at::Tensor k_pages, at::Tensor v_pages,
+    std::optional<at::Tensor> k_scales, std::optional<at::Tensor> v_scales,
+    at::Tensor block_table, at::Tensor seq_lens, at::Tensor q_lens,
+    std::optional<at::Tensor> out, std::optional<at::Tensor> lse,
+    std::optional<at::Tensor> o_part, std::optional<at::Tensor> m_part,
+    std::optional<at::Tensor> l_part,
+    double scale, bool causal, int64_t win, bool has_win, int64_t kv_split) {
+    // q bf16 (B,T,H,D); pool operands as decode_partial_paged; q_lens int32
+    // (B,).  kv_split <= 1 writes out bf16 (B,T,H,D) + lse fp32 (B,H,T);
+    // kv_split > 1 writes the (S,B,H,D,T) + m,l partials for attn_fwd_merge.
+    CHECK_BF16_CONTIG(q);
+    TORCH_CHECK(q.dim() == 4, "q must be (B,T,H,D)");
+    const int64_t B = q.size(0), T = q.size(1), H = q.size(2), D = q.size(3);
+    bool fp8 = false;
+    const int shift = check_paged_pool(q, k_pages, v_pages, k_scales, v_scales,
+                                       block_table, seq_lens, B, D, &fp8);
+    const int64_t HK = k_pages.size(1);
+    TORCH_CHECK(H % HK == 0, "q heads must be a multiple of kv heads");
+    TORCH_CHECK(q_lens.scalar_type() == at::kInt && q_lens.is_contiguous()
+                && q_lens.dim() == 1 && q_lens.size(0) == B
+                && q_lens.device() == q.device(),
+                "q_lens must be contiguous int32 (B,) on the same device");
+    TORCH_CHECK(B * H <= 65535, "B*H must fit grid.y");
+    TORCH_CHECK(T < (int64_t(1) << 31), "T too large");
+    TORCH_CHECK(!has_win || win >= 0, "window must be >= 0");
+    PagedPrefillParams p{};
+    if (kv_split > 1) {
+        TORCH_CHECK(kv_split <= 16, "kv_split capped at 16");
+        TORCH_CHECK(o_part && m_part && l_part, "split launches need partial o/m/l buffers");
+        CHECK_F32_CONTIG((*o_part)); CHECK_F32_CONTIG((*m_part)); CHECK_F32_CONTIG((*l_part));
+        TORCH_CHECK(o_part->numel() == kv_split * B * H * D * T
+                    && m_part->numel() == kv_split * B * H * T
+                    && l_part->numel() == kv_split * B * H * T,
+                    "partials must be (S,B,H,D,T) and (S,B,H,T)");
+        p.o_part = o_part->data_ptr<float>();
+        p.m_part = m_part->data_ptr<float>();
+        p.l_part = l_part->data_ptr<float>();
+    } else {
+        TORCH_CHECK(out && lse, "unsplit launches need out/lse");
+        CHECK_BF16_CONTIG((*out)); CHECK_F32_CONTIG((*lse));
+        TORCH_CHECK(out->sizes() == q.sizes() && lse->numel() == B * H * T);
+        p.out = out->data_ptr();
+        p.lse = lse->data_ptr<float>();
+    }
+    if (B * T * H == 0) return;
+    p.q = q.data_ptr();
+    p.k_pages = k_pages.data_ptr(); p.v_pages = v_pages.data_ptr();
+    if (fp8) { p.kscale = k_scales->data_ptr(); p.vscale = v_scales->data_ptr(); }
+    p.block_table = block_table.data_ptr<int>();
+    p.seq_lens = seq_lens.data_ptr<int>();
+    p.q_lens = q_lens.data_ptr<int>();
+    p.b = (int)B; p.h = (int)H; p.hk = (int)HK; p.t = (int)T;
+    p.page_shift = shift;
+    p.max_pages = (int)block_table.size(1);
+    p.num_pages = (int)k_pages.size(0);
+    p.causal = causal ? 1 : 0; p.has_win = has_win ? 1 : 0; p.win = win;
+    p.scale = (float)scale;
+    p.kv_split = (int)kv_split;
+    launch_attn_fwd_paged(p, (int)D, fp8, at::hip::getCurrentHIPStream());
+    TORCH_CHECK(hipGetLastError() == hipSuccess, "paged prefill launch failed");
+}
+
 at::Tensor attn_delta(at::Tensor dout, at::Tensor out) {
     // dout, out (B,N,H,D) bf16 -> delta fp32 (B,H,N) = rowsum(dout*out)
     CHECK_BF16_CONTIG(dout); CHECK_BF16_CONTIG(out);
@@ -665,6 +728,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::arg("k_new"), py::arg("v_new"), py::arg("k_pages"),
             py::arg("v_pages"), py::arg("k_scales"), py::arg("v_scales"),
             py::arg("block_table"), py::arg("seq_lens"), py::arg("append_lens"));
+    mod.def("attn_fwd_paged", &ring_attn::attn_fwd_paged,
+            "CDNA4 paged prefill attention (bf16 or fp8 pages, per-sequence lengths)",
+            py::arg("q"), py::arg("k_pages"), py::arg("v_pages"),
+            py::arg("k_scales"), py::arg("v_scales"), py::arg("block_table"),
+            py::arg("seq_lens"), py::arg("q_lens"), py::arg("out"), py::arg("lse"),
+            py::arg("o_part"), py::arg("m_part"), py::arg("l_part"),
+            py::arg("scale"), py::arg("causal"), py::arg("win"),
+            py::arg("has_win"), py::arg("kv_split"));
     // host access to attn_mask.h, the kernels' own mask geometry (no GPU
     // needed): the descriptor builder takes its shapes and bounds from here,
     // and the CPU tests hold it to a brute-force mask

@@ -24,6 +24,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "attn_fwd.hip"),
         os.path.join(CSRC, "attn_fwd_v2.hip"),
         os.path.join(CSRC, "attn_fwd_fp8.hip"),
+        os.path.join(CSRC, "attn_fwd_paged.hip"),
         os.path.join(CSRC, "attn_bwd.hip"),
         os.path.join(CSRC, "decode.hip"),
         os.path.join(CSRC, "decode_paged.hip"),
