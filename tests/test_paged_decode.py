@@ -233,15 +233,9 @@ def test_paged_append_bf16(d):
     assert cache.seq_lens.cpu().tolist() == want and cache.host_lens == want
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("d", [64, 128])
-def test_paged_append_fp8(d):
-    """Fused quantising append == quantize_kv_cache on the same rows: scale
-    bytes identical, dequantised values torch.equal (+-0 compare equal)."""
-    torch.manual_seed(22)
-    cache, k_new, v_new = _append_setup(d, fp8=True)
-    cache.append(k_new, v_new, APPEND_LENS)
-    torch.cuda.synchronize()
+def _check_append_fp8(cache, k_new, v_new):
+    """Appended rows bit-equal to quantize_kv_cache (scale bytes identical,
+    dequantised values torch.equal), every other row untouched."""
     k8, v8, ks, vs = quantize_kv_cache(k_new.cpu(), v_new.cpu())
     written = torch.zeros(cache.k_scales.shape, dtype=torch.bool)
     for pool, scales, ref8, refs, src in (
@@ -263,6 +257,36 @@ def test_paged_append_fp8(d):
         assert (scales[~written] == 0x5a).all()
     want = [a + b for a, b in zip(APPEND_START, APPEND_LENS)]
     assert cache.seq_lens.cpu().tolist() == want and cache.host_lens == want
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("d", [64, 128])
+def test_paged_append_fp8(d):
+    """Fused quantising append == quantize_kv_cache on the same rows: scale
+    bytes identical, dequantised values torch.equal (+-0 compare equal)."""
+    torch.manual_seed(22)
+    cache, k_new, v_new = _append_setup(d, fp8=True)
+    cache.append(k_new, v_new, APPEND_LENS)
+    torch.cuda.synchronize()
+    _check_append_fp8(cache, k_new, v_new)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("d", [64, 128])
+def test_paged_append_fp8_gains(d):
+    """The same append (13 + 8 crosses a page) with every appended row at its
+    own gain 2^[-4, 4]: neighbouring rows carry different scale bytes, so a
+    scale written to the wrong row or page breaks the bit-equality."""
+    torch.manual_seed(23)
+    cache, k_new, v_new = _append_setup(d, fp8=True)
+    gains = lambda: torch.exp2(torch.randint(-4, 5, k_new.shape[:3] + (1,)).float()).cuda()
+    k_new = (k_new.float() * gains()).to(torch.bfloat16)
+    v_new = (v_new.float() * gains()).to(torch.bfloat16)
+    _, _, ks, vs = quantize_kv_cache(k_new.cpu(), v_new.cpu())
+    assert ks.unique().numel() >= 5 and vs.unique().numel() >= 5
+    cache.append(k_new, v_new, APPEND_LENS)
+    torch.cuda.synchronize()
+    _check_append_fp8(cache, k_new, v_new)
 
 
 @pytest.mark.gpu
@@ -290,6 +314,31 @@ def test_paged_fp8_decode(d):
     ks, vs = _pool_rows(cache.k_pages, cache.v_pages, cache.block_table, lens, d,
                         cache.k_scales, cache.v_scales)
     _check(out, lse, *_oracle(q, ks, vs, False), OUT_FP8, "fp8")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ps", [16, 64])
+def test_paged_fp8_decode_gains(ps):
+    """Rows at their own gains 2^[-4, 4] through the fp8 append, queries
+    leaning on the rows around page and 64-key boundaries (15|16, 63|64,
+    127|128, 511|512).  Judged relative to mag = softmax |v| against the fp64
+    oracle on the dequantised pool: bound B_FP32 (tests/fp8_emulation.py:
+    fp32 eager floor 1.0e-6, neighbour-scale ceiling 0.205)."""
+    from .fp8_emulation import (B_FP32, CACHE_GAINS_CASES, build_gains_cache,
+                                relative_failures, rows_oracle)
+    lens, hk, h, nq, d, edges = CACHE_GAINS_CASES["paged_decode"]
+    q, k, v = build_gains_cache(lens, hk, h, nq, d, edges)
+    cache = PagedKVCache.from_dense(k.cuda(), v.cuda(), lens, ps, fp8=True,
+                                    shuffle_seed=5, spare_pages=2)
+    out, lse = _local_paged_decode_partial(q.cuda(), cache)
+    ks, vs = _pool_rows(cache.k_pages, cache.v_pages, cache.block_table, lens, d,
+                        cache.k_scales, cache.v_scales)
+    heads = torch.arange(h) % hk
+    for i in range(len(lens)):
+        ref, mag, ref_lse = rows_oracle(q[i], ks[i][heads], vs[i][heads], d ** -0.5)
+        relative_failures(out[i], ref, mag, B_FP32, f"paged fp8 gains ps{ps} seq {i}")
+        e_lse = (lse[i, ..., 0].double().cpu() - ref_lse).abs().max().item()
+        assert e_lse < LSE_TOL, f"lse err {e_lse}"
 
 
 @pytest.mark.gpu

@@ -188,6 +188,43 @@ def test_prefill_fp8_pool(page_size, d, causal, kv_split):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("kv_split", [1, 3])
+@pytest.mark.parametrize("page_size", [16, 128])
+def test_prefill_fp8_pool_gains(page_size, kv_split):
+    """fp8 pool whose rows carry their own gains 2^[-4, 4], 40 tail queries
+    per sequence leaning on the rows around page and kv-tile boundaries
+    (15|16, 63|64, 127|128, 255|256), causal.  Judged relative to
+    mag = softmax |v| against the fp64 oracle on the dequantised pool; the
+    output is bf16, so the bound is B_BF16 = 2**-6 (tests/fp8_emulation.py:
+    fp32 eager floor 1.6e-6, neighbour-scale ceiling 0.52)."""
+    from .fp8_emulation import (B_BF16, CACHE_GAINS_CASES, build_gains_cache,
+                                relative_failures, rows_oracle)
+    lens, hk, h, nq, d, edges = CACHE_GAINS_CASES["prefill"]
+    key = ("gains", page_size)
+    if key not in _memo:
+        q, k, v = build_gains_cache(lens, hk, h, nq, d, edges)
+        cache = PagedKVCache.from_dense(k.cuda(), v.cuda(), lens, page_size, fp8=True,
+                                        shuffle_seed=5, spare_pages=3)
+        ks, vs = _pool_rows(cache.k_pages, cache.v_pages, cache.block_table, lens, d,
+                            cache.k_scales, cache.v_scales)
+        heads = torch.arange(h) % hk
+        refs = []
+        for i, n in enumerate(lens):
+            vis = torch.arange(n)[None, :] <= (n - nq + torch.arange(nq))[:, None]
+            refs.append(rows_oracle(q[i], ks[i][heads], vs[i][heads], d ** -0.5, vis))
+        _memo[key] = (q.transpose(1, 2).contiguous().cuda(), cache, refs)
+    qt, cache, refs = _memo[key]
+    out, lse = paged_prefill_attn(qt, cache, [nq] * len(lens), causal=True,
+                                  return_lse=True, kv_split=kv_split)
+    torch.cuda.synchronize()
+    for i, (ref, mag, ref_lse) in enumerate(refs):
+        relative_failures(out[i].transpose(0, 1), ref, mag, B_BF16,
+                          f"prefill fp8 gains ps{page_size} s{kv_split} seq {i}")
+        e_lse = (lse[i].double().cpu() - ref_lse).abs().max().item()
+        assert e_lse < LSE_TOL, f"lse err {e_lse}"
+
+
+@pytest.mark.gpu
 def test_prefill_agrees_with_decode():
     """T = 4 tail queries, causal: the prefill kernel against the paged
     decode kernel (same convention: the queries' tokens are already cached)."""
