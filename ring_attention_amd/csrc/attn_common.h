@@ -389,7 +389,11 @@ struct PagedPrefillParams {
 void launch_attn_fwd_paged(const PagedPrefillParams& p, int head_dim, bool fp8,
                            hipStream_t stream);
 
-struct Fp8FwdParams {
+// Fp8FwdCore is all a launch with the standard mask reads, and all that the
+// instantiations with the constant mask take as their kernel argument (the
+// PAIRED kernels keep a copy in a stack frame); the launcher hands the
+// geometry of Fp8FwdParams only to the instantiations that read it.
+struct Fp8FwdCore {
     const void* q;      // e4m3 bytes (B, Nq, H, D)
     const void* k;      // e4m3 bytes (B, Nk, H, D)
     const void* vt;     // e4m3 bytes (B, H, D, Nk)  — host-pre-transposed V
@@ -404,8 +408,16 @@ struct Fp8FwdParams {
     long nk_true;       // true kv length: keys j >= nk_true are masked out
     int nvs;            // Nk / 64
     float scale;
-    int causal;         // standard causal (qpos(i) = i), paired-tile grid
-    int paired;         // total q tiles T (causal launcher)
+    int causal;         // j <= qpos(i)
+    int paired;         // total q tiles T (PAIRED launches)
+};
+
+struct Fp8FwdParams : Fp8FwdCore {
+    // mask geometry (attn_mask.h): qpos(i) = i * q_stride + diag, window
+    // qpos(i) - j <= win when has_win.  diag 0, q_stride 1, no window is the
+    // standard mask and runs the instantiations with the constant mask.
+    int has_win;
+    long diag, q_stride, win;
 };
 
 void launch_attn_fwd_fp8(const Fp8FwdParams& p, int head_dim, hipStream_t stream);

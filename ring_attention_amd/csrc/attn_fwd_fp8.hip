@@ -39,7 +39,14 @@
 // per WG instead of the 2:1 triangle imbalance).  GQA pairs q head qh with
 // kv head qh % hk (reference tile convention).
 //
-// Scope (asserted in the binding): no mask/bias/window/softclamp, single
+// Mask: attn_mask.h's geometry (causal at qpos(i) = i * q_stride + diag, an
+// optional window qpos(i) - j <= win), so a ring hop of any layout is one
+// launch; the walk covers kv_tile_range only.  Rows that attend no key give
+// out == 0 and the finite lse floor log(1e-38) + MASK_VALUE_F * ln 2: a masked
+// score is MASK_VALUE_F, m_exp is clamped at -1.7e38, so exp2 sees -1.7e38
+// (P = 0, never inf - inf), and alpha = exp2(MASK_VALUE_F - MASK_VALUE_F) = 1.
+//
+// Scope (asserted in the binding): no key-pad mask/bias/softclamp, single
 // shot (no ring resume), D in {64, 128}.  Ragged lengths are handled by the
 // PYTHON wrapper padding the quantized buffers to (nq%256, nk%128)
 // alignment (zero rows, scale 2^-127 — never NaN bytes) while the kernel
@@ -49,6 +56,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 #include <cstdint>
+#include <type_traits>
 
 #include "attn_common.h"
 
@@ -71,9 +79,16 @@ struct Fp8Lds {
     unsigned char ks[2][FP8_KVBLK * (D / 64)];           // k (row, chunk) e8m0
 };
 
-template <int D, bool PAIRED>
+// GEO selects the mask: false folds the standard mask (qpos(i) = i, no window)
+// to constants, true reads diag / q_stride / win from the params.  Without
+// GEO the kernel takes the core of the params alone, so its kernarg and the
+// PAIRED frame's copy of it are what they were before the geometry existed.
+template <bool GEO>
+using Fp8Frame = std::conditional_t<GEO, Fp8FwdParams, Fp8FwdCore>;
+
+template <int D, bool PAIRED, bool GEO>
 __global__ __launch_bounds__(FP8_NTHREADS, 1)
-void attn_fwd_fp8_kernel(Fp8FwdParams p) {
+void attn_fwd_fp8_kernel(Fp8Frame<GEO> p) {
     constexpr int DBLK = D / 32;
     constexpr int NDCH = D / 64;          // 64-deep MFMA k-chunks per head dim
     constexpr int KCH = D * 2 / 32;       // 16B LDS chunks per K row (D bytes)
@@ -102,7 +117,7 @@ void attn_fwd_fp8_kernel(Fp8FwdParams p) {
     }
 
     auto fp8_body = [&]() {
-    const Fp8FwdParams P = p;             // register-local (noinline frame)
+    const Fp8Frame<GEO> P = p;            // register-local (noinline frame)
     const long i = (long)qtile * FP8_QROWS_WG + wid * FP8_QROWS_WAVE + l31;
 
     // ---- Q fragments: per 64-d chunk, 32 e4m3 bytes (d = 64*dc + 32*lhi
@@ -125,13 +140,22 @@ void attn_fwd_fp8_kernel(Fp8FwdParams p) {
     #pragma unroll
     for (int db = 0; db < DBLK; ++db) o_acc[db] = f32x16{};
 
-    // ---- causal tile range for this workgroup (attn_mask.h): standard
-    // causal, qpos(i) = i, no window.  nq and nk are padded to whole tiles,
-    // so the walk covers the padded keys and masks them at nk_true below.
-    const Mask M{P.causal, 0, 0, 1, 0};
+    // ---- kv tile range [t_lo, t_hi) of this workgroup (attn_mask.h; it
+    // takes ROW indices and applies qpos itself).  nq and nk are padded to
+    // whole tiles, so the walk covers the padded keys and masks them at
+    // nk_true below.  An empty range falls straight to the epilogue.
+    const Mask M = [&P] {
+        if constexpr (GEO) return mask_of(P);
+        else return Mask{P.causal, 0, 0, 1, 0};
+    }();
     const long wg_q_min = (long)qtile * FP8_QROWS_WG;
     const long wg_q_max = wg_q_min + FP8_QROWS_WG - 1;
-    const int t_hi = M.kv_tile_range(wg_q_min, wg_q_max, P.nk, FP8_KVBLK).hi;
+    const TileRange tr = M.kv_tile_range(wg_q_min, wg_q_max, P.nk, FP8_KVBLK);
+    const int t_hi = tr.hi;
+    const int t_lo = GEO ? tr.lo : 0;
+    // the one 64-bit position of this lane's row; per tile it becomes a
+    // 32-bit offset range (Mask::row_cut), never a position per element
+    const long qp = M.qpos(i);
 
     // ---- staging (one uint4 per thread per image per tile)
     const unsigned char* kbase = (const unsigned char*)P.k
@@ -149,6 +173,11 @@ void attn_fwd_fp8_kernel(Fp8FwdParams p) {
     const unsigned char* kptr = kbase + (tid / KCH) * k_row_stride + (tid % KCH) * 16;
     const unsigned char* vptr = vtbase + (long)(tid / VCH) * P.nk + (tid % VCH) * 16;
     const unsigned char* ksptr = ksbase + (long)(tid / NDCH) * P.hk * NDCH + (tid % NDCH);
+    if constexpr (GEO) {                  // a window starts the walk at t_lo
+        kptr += (long)t_lo * FP8_KVBLK * k_row_stride;
+        vptr += (long)t_lo * FP8_KVBLK;
+        ksptr += (long)t_lo * FP8_KVBLK * P.hk * NDCH;
+    }
 
     uint4 kst[KREGS], vst[KREGS];
     unsigned char ksst = 0;
@@ -183,17 +212,18 @@ void attn_fwd_fp8_kernel(Fp8FwdParams p) {
 
     const float scale2 = P.scale * LOG2E;
 
-    if (t_hi > 0) {
+    if (t_hi > t_lo) {
         load_tile();
         write_tile(0);
-        if (t_hi > 1) load_tile();
+        if (t_hi > t_lo + 1) load_tile();
     }
 
-    for (int t = 0; t < t_hi; ++t) {
-        const int par = t & 1;
+    for (int t = t_lo; t < t_hi; ++t) {
+        const int par = (t - t_lo) & 1;
         const long j0 = (long)t * FP8_KVBLK;
+        // uncut wants q POSITIONS (qpos is monotone in the row index)
         const bool full_tile = (j0 + FP8_KVBLK <= P.nk_true)
-            && M.uncut(wg_q_min, wg_q_max, j0, j0 + FP8_KVBLK - 1);
+            && M.uncut(M.qpos(wg_q_min), M.qpos(wg_q_max), j0, j0 + FP8_KVBLK - 1);
 
         __syncthreads();
 
@@ -234,6 +264,22 @@ void attn_fwd_fp8_kernel(Fp8FwdParams p) {
                 #pragma unroll
                 for (int r = 0; r < 16; ++r) smax = fmaxf(smax, s[kb][r]);
             smax *= scale2;
+        } else if constexpr (GEO) {
+            // padded keys, causal and window as one offset range per row
+            // (the lane half's 4 * lhi goes into the range, so that the
+            // element offsets compared against it are compile-time constants)
+            const RowCut rc = M.row_cut(qp, j0, FP8_KVBLK, P.nk_true);
+            const int o_lo = rc.lo - 4 * lhi, o_hi = rc.hi - 4 * lhi;
+            #pragma unroll
+            for (int kb = 0; kb < FP8_NBLK; ++kb)
+                #pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int o = kb * 32 + (r & 3) + 8 * (r >> 2);
+                    float x = s[kb][r] * scale2;
+                    if (o < o_lo || o > o_hi) x = MASK_VALUE_F;
+                    s[kb][r] = x;
+                    smax = fmaxf(smax, x);
+                }
         } else {
             #pragma unroll
             for (int kb = 0; kb < FP8_NBLK; ++kb)
@@ -242,7 +288,7 @@ void attn_fwd_fp8_kernel(Fp8FwdParams p) {
                     long j = j0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
                     float x = s[kb][r] * scale2;
                     // padded keys, then the mask at qpos(i) = i
-                    if (!M.attends(i, j, j < P.nk_true)) x = MASK_VALUE_F;
+                    if (!M.attends(qp, j, j < P.nk_true)) x = MASK_VALUE_F;
                     s[kb][r] = x;
                     smax = fmaxf(smax, x);
                 }
@@ -354,23 +400,52 @@ void attn_fwd_fp8_kernel(Fp8FwdParams p) {
     }  // pair loop
 }
 
+template <int D, bool PAIRED, bool GEO>
+static void launch_fp8_instance(const Fp8FwdParams& p, dim3 grid, hipStream_t stream) {
+    const Fp8Frame<GEO> arg = p;          // without GEO: the core (slicing)
+    hipLaunchKernelGGL((attn_fwd_fp8_kernel<D, PAIRED, GEO>), grid,
+                       dim3(FP8_NTHREADS), 0, stream, arg);
+}
+
+// Which instantiation a launch runs:
+//   A causal mask whose row 0 already sees the last true key (diag >=
+//   nk_true - 1: a ring hop from an earlier rank) cuts nothing and is
+//   launched as not causal.  Then
+//   GEO    is off when the mask is the standard one: no window and either
+//          not causal (diag / q_stride do not matter) or diag == 0 with
+//          q_stride == 1.  Those launches keep the constant-folded mask.
+//   PAIRED (WG x runs q tiles (x, T-1-x)) when the mask is causal, has no
+//          window, q_stride == 1 and the diagonal cuts the hop: row 0 misses
+//          a key (the rule above) and the last row sees one.  That covers
+//          the standard causal call and every striped ring hop (diag 0 /
+//          -1).  A window bounds every row's walk and a stride or a diagonal
+//          outside the hop leaves no triangle to balance: those take the
+//          plain grid.
 void launch_attn_fwd_fp8(const Fp8FwdParams& p, int head_dim, hipStream_t stream) {
     const long T = p.nq / FP8_QROWS_WG;
-    dim3 block(FP8_NTHREADS);
-    if (p.causal) {
-        Fp8FwdParams pc = p;
-        pc.paired = (int)T;
-        dim3 grid((unsigned)((T + 1) / 2), (unsigned)(p.b * p.h));
-        if (head_dim == 64)
-            hipLaunchKernelGGL((attn_fwd_fp8_kernel<64, true>), grid, block, 0, stream, pc);
-        else
-            hipLaunchKernelGGL((attn_fwd_fp8_kernel<128, true>), grid, block, 0, stream, pc);
+    const bool causal = p.causal && p.diag < p.nk_true - 1;
+    const bool geo = p.has_win || (causal && (p.diag != 0 || p.q_stride != 1));
+    const bool cuts = p.nq - 1 + p.diag >= 0;
+    const bool paired = causal && !p.has_win && p.q_stride == 1 && cuts;
+    Fp8FwdParams pc = p;
+    pc.causal = causal ? 1 : 0;
+    pc.paired = (int)T;
+    const dim3 grid((unsigned)(paired ? (T + 1) / 2 : T), (unsigned)(p.b * p.h));
+    const bool d64 = head_dim == 64;
+    // (the standard-mask instantiations are named first, in the order they
+    // always had: the PAIRED frame functions are 4-byte aligned, so where
+    // they land in the code object follows from what is emitted before them,
+    // and a hot loop moved against the fetch window cost 0.2 - 0.6%)
+    if (!geo) {
+        if (paired) d64 ? launch_fp8_instance<64, true, false>(pc, grid, stream)
+                        : launch_fp8_instance<128, true, false>(pc, grid, stream);
+        else        d64 ? launch_fp8_instance<64, false, false>(pc, grid, stream)
+                        : launch_fp8_instance<128, false, false>(pc, grid, stream);
     } else {
-        dim3 grid((unsigned)T, (unsigned)(p.b * p.h));
-        if (head_dim == 64)
-            hipLaunchKernelGGL((attn_fwd_fp8_kernel<64, false>), grid, block, 0, stream, p);
-        else
-            hipLaunchKernelGGL((attn_fwd_fp8_kernel<128, false>), grid, block, 0, stream, p);
+        if (paired) d64 ? launch_fp8_instance<64, true, true>(pc, grid, stream)
+                        : launch_fp8_instance<128, true, true>(pc, grid, stream);
+        else        d64 ? launch_fp8_instance<64, false, true>(pc, grid, stream)
+                        : launch_fp8_instance<128, false, true>(pc, grid, stream);
     }
 }
 

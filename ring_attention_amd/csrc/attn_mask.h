@@ -31,6 +31,7 @@ constexpr int FP8_KVBLK = 128;    // fp8 forward kv tile, every head dim
 constexpr long ceil_div(long a, long b) { return (a + b - 1) / b; }
 
 struct TileRange { int lo, hi; };   // tiles [lo, hi)
+struct RowCut { int lo, hi; };      // key offsets [lo, hi] of one tile, inclusive
 
 struct Mask {
     int causal, has_win;
@@ -46,6 +47,21 @@ struct Mask {
         if (causal) ok = ok && (j <= qp);
         if (has_win) ok = ok && (qp - j <= win);
         return ok;
+    }
+
+    // the per-element test of one q position against the W keys of the tile
+    // that starts at j0, reduced to 32-bit offsets: key j0 + o (0 <= o < W)
+    // attends  <=>  lo <= o <= hi  <=>  attends(qp, j0 + o, j0 + o < nk).
+    // All 64-bit arithmetic happens here, once per (row, tile); an empty
+    // row gives lo > hi.
+    RING_ATTN_MASK_FN RowCut row_cut(long qp, long j0, int W, long nk) const {
+        long hi = nk - 1 - j0, lo = 0;
+        if (hi > W - 1) hi = W - 1;
+        if (causal && qp - j0 < hi) hi = qp - j0;
+        if (has_win && qp - win - j0 > lo) lo = qp - win - j0;
+        if (hi < -1) hi = -1;
+        if (lo > W) lo = W;
+        return {(int)lo, (int)hi};
     }
 
     // no pair of (q positions [q_lo, q_hi]) x (keys [j0, jmax]) is cut by

@@ -361,8 +361,12 @@ std::vector<at::Tensor> decode_partial(at::Tensor q, at::Tensor k, at::Tensor v,
 
 std::vector<at::Tensor> attn_fwd_fp8(at::Tensor q8, at::Tensor k8, at::Tensor v8t,
                                       at::Tensor qs, at::Tensor ks, at::Tensor vs,
-                                      double sm_scale, bool causal, int64_t nk_true) {
-    // MX-FP8 serving forward (see attn_fwd_fp8.hip header for scope):
+                                      double sm_scale, bool causal, int64_t nk_true,
+                                      int64_t diag, int64_t q_stride, bool has_win,
+                                      int64_t win) {
+    // MX-FP8 serving forward (see attn_fwd_fp8.hip header for scope); the
+    // mask is attn_mask.h's: causal at qpos(i) = i * q_stride + diag, window
+    // qpos(i) - j <= win when has_win (the defaults are the standard mask):
     //   q8 (B,Nq,H,D) u8 e4m3; k8 (B,Nk,H,D) u8; v8t (B,H,D,Nk) u8
     //   qs (B,Nq,H) u8 e8m0(+127); ks (B,Nk,H) u8; vs (B,H,D,Nk/64) u8
     // -> out bf16 (B,Nq,H,D), lse fp32 (B,H,Nq)
@@ -376,6 +380,7 @@ std::vector<at::Tensor> attn_fwd_fp8(at::Tensor q8, at::Tensor k8, at::Tensor v8
     TORCH_CHECK(H % HK == 0, "fp8 path: q heads must be a multiple of kv heads");
     TORCH_CHECK(NQ % 256 == 0, "fp8 path: nq must be a multiple of 256 (v0)");
     TORCH_CHECK(NK % 128 == 0, "fp8 path: nk must be a multiple of 128 (v0)");
+    TORCH_CHECK(q_stride >= 1, "fp8 path: q_stride must be >= 1");
     if (nk_true <= 0) nk_true = NK;
     TORCH_CHECK(v8t.size(1) == HK && v8t.size(3) == NK && v8t.size(2) == D
                 && vs.size(1) == HK && vs.size(3) == NK / 64);
@@ -392,6 +397,8 @@ std::vector<at::Tensor> attn_fwd_fp8(at::Tensor q8, at::Tensor k8, at::Tensor v8
     p.nk_true = nk_true;
     p.nvs = (int)(NK / 64);
     p.causal = causal ? 1 : 0;
+    p.has_win = has_win ? 1 : 0;
+    p.diag = diag; p.q_stride = q_stride; p.win = has_win ? win : 0;
     p.scale = sm_scale > 0 ? (float)sm_scale : (float)(1.0 / std::sqrt((double)D));
     launch_attn_fwd_fp8(p, (int)D, at::hip::getCurrentHIPStream());
     TORCH_CHECK(hipGetLastError() == hipSuccess, "attn_fwd_fp8 launch failed");
@@ -709,7 +716,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             "CDNA4 MX-FP8 serving forward (e4m3 + e8m0 row scales)",
             py::arg("q8"), py::arg("k8"), py::arg("v8t"), py::arg("qs"),
             py::arg("ks"), py::arg("vs"), py::arg("sm_scale") = -1.0,
-            py::arg("causal") = false, py::arg("nk_true") = 0);
+            py::arg("causal") = false, py::arg("nk_true") = 0,
+            py::arg("diag") = 0, py::arg("q_stride") = 1,
+            py::arg("has_win") = false, py::arg("win") = 0);
     mod.def("decode_partial_fp8", &ring_attn::decode_partial_fp8,
             "CDNA4 FP8 KV-cache decode partial",
             py::arg("q"), py::arg("k8"), py::arg("v8"), py::arg("ks"),
@@ -757,6 +766,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
                          a.data_ptr<bool>()[i * nk + j] = m.attends(m.qpos(i), j);
                  return a;
              })
+        .def("row_cut", [](const Mask& m, long qp, long j0, int w, long nk) {
+                 auto r = m.row_cut(qp, j0, w, nk);
+                 return std::make_pair(r.lo, r.hi); },
+             py::arg("qpos"), py::arg("j0"), py::arg("w"), py::arg("nk"))
         .def("uncut", &Mask::uncut, py::arg("q_lo"), py::arg("q_hi"), py::arg("j0"), py::arg("jmax"))
         .def("kv_tile_range", [pair](const Mask& m, long i_min, long i_max, long nk, int w) {
                  return pair(m.kv_tile_range(i_min, i_max, nk, w)); })

@@ -88,9 +88,10 @@ class RingAttention(nn.Module):
         self.softclamp_value = softclamp_value
         self.use_hip_kernel = use_hip_kernel  # None = auto (on GPU)
         # MX-FP8 inference: no-grad forwards route to the e4m3 serving path
-        # (ops/fp8.py) when its scope applies — non-striped, no mask/bias/
-        # softclamp/lookback.  Training steps and out-of-scope calls keep
-        # the bf16 path automatically.
+        # (ops/fp8.py) when its scope applies — no mask/bias/softclamp;
+        # striped_ring_attn and max_lookback_seq_len are in scope (the fp8
+        # kernel takes the bf16 path's hop geometry).  Training steps and
+        # out-of-scope calls keep the bf16 path automatically.
         self.fp8_inference = fp8_inference
 
         assert not (striped_ring_attn and not causal), "striped ring attention requires causal"
@@ -174,15 +175,20 @@ class RingAttention(nn.Module):
 
     def _flash(self, q, k, v, mask, ring_reduce: bool, ring_size: int) -> Tensor:
         if (self.fp8_inference and not torch.is_grad_enabled()
-                and mask is None and not self.striped_ring_attn
-                and not self.softclamp_qk_sim
-                and self.max_lookback_seq_len is None):
+                and mask is None and not self.softclamp_qk_sim):
             from ..ops.fp8 import flash_attn_fp8, ring_flash_attn_fp8
             if ring_reduce:
                 out, _ = ring_flash_attn_fp8(
-                    q, k, v, ring_size=ring_size, causal=self.causal)
+                    q, k, v, ring_size=ring_size, causal=self.causal,
+                    striped=self.striped_ring_attn,
+                    max_lookback_seq_len=self.max_lookback_seq_len)
             else:
-                out, _ = flash_attn_fp8(q, k, v, causal=self.causal)
+                # no ring: the bf16 branch treats this as a ring of one
+                # (RingFlashAttentionHIPFunction.forward), where striped is
+                # the plain causal mask and the lookback counts local
+                # positions.  The fp8 side does the same.
+                out, _ = flash_attn_fp8(q, k, v, causal=self.causal,
+                                        window=self.max_lookback_seq_len)
             return out
         use_hip = self.use_hip_kernel if self.use_hip_kernel is not None else q.is_cuda
         if use_hip and q.is_cuda:

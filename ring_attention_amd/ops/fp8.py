@@ -22,18 +22,34 @@ and to 7.6e-6 in lse (MI355X, tests/test_fp8_emulation.py).
 Causal (``causal=True``) uses the bf16 kernels' mirrored paired-tile
 load balance; GQA follows the framework-wide ``qh % hk`` pairing.
 
+Mask: the bf16 kernels' geometry (docs/KERNELS.md section 1),
+
+    attend(i, j) <=> j < nk_true and (not causal or j <= qpos(i))
+                     and (window is None or qpos(i) - j <= window),
+    qpos(i) = i * q_stride + diag,
+
+so a ring hop of any layout (rank-ordered, striped, with lookback) is one
+launch.  A row that attends no key returns out == 0 and lse == LSE_FLOOR,
+a finite stand-in for log(0) that `merge_fp8_partials` combines without NaN.
+
 Scope: forward only (use the bf16 path for training); no bias/key-pad
-mask/window; any head dim <= 128 (native 64/128 + exact zero-pad).
+mask/softclamp; any head dim <= 128 (native 64/128 + exact zero-pad).
 Ragged lengths are handled by padding the quantized buffers (zero bytes —
 a valid e4m3, never NaN) while the kernel masks at the true kv length.
 """
 
 from __future__ import annotations
 
+import math
+
 import torch
 from torch import Tensor
 
 from . import hip_ext
+
+# lse of a row that attends no key, as the kernel's epilogue forms it:
+# log(max(l, 1e-38)) + m * ln 2 with l = 0 and m = MASK_VALUE_F (-FLT_MAX)
+LSE_FLOOR = math.log(1e-38) + -3.4028234663852886e38 * 0.6931471805599453
 
 
 def _e8m0(amax: Tensor) -> tuple[Tensor, Tensor]:
@@ -94,12 +110,16 @@ def flash_attn_fp8(
     q: Tensor, k: Tensor, v: Tensor,
     sm_scale: float | None = None,
     causal: bool = False,
+    window: int | None = None,
+    causal_mask_diagonal: bool = False,
 ) -> tuple[Tensor, Tensor]:
     """MX-FP8 attention forward on (b, n, h, d) tensors.
 
     Returns (out bf16 (b, n, h, d), lse fp32 (b, h, n)).  Quantizes
     internally; pass pre-quantized operands via flash_attn_fp8_quantized
-    to amortize quantization across decode steps.
+    to amortize quantization across decode steps.  `window` keeps keys with
+    i - j <= window; `causal_mask_diagonal` masks the diagonal too (j < i),
+    both as in `flash_attn`.
     """
     d = q.shape[-1]
     sm = sm_scale if sm_scale is not None else d ** -0.5
@@ -116,18 +136,26 @@ def flash_attn_fp8(
     q8, k8, v8t, qs, ks, vs = quantize_fp8(q, k, v)
     out, lse = flash_attn_fp8_quantized(
         q8, k8, v8t, qs, ks, vs, sm,
-        causal=causal, nk_true=k.shape[1])
+        causal=causal, nk_true=k.shape[1],
+        diag=-1 if (causal and causal_mask_diagonal) else 0, window=window)
     nq = q.shape[1]
     return out[:, :nq, :, :d], lse[..., :nq]
 
 
 def flash_attn_fp8_quantized(q8, k8, v8t, qs, ks, vs, sm_scale: float,
-                             causal: bool = False, nk_true: int = 0):
+                             causal: bool = False, nk_true: int = 0,
+                             diag: int = 0, q_stride: int = 1,
+                             window: int | None = None):
+    """The fused forward on quantize_fp8's operands, masked by the module
+    docstring's geometry (the defaults are the standard mask)."""
     if q8.is_cuda:
-        out, lse = hip_ext.require().attn_fwd_fp8(q8, k8, v8t, qs, ks, vs,
-                                                  sm_scale, causal, nk_true)
+        out, lse = hip_ext.require().attn_fwd_fp8(
+            q8, k8, v8t, qs, ks, vs, sm_scale, causal, nk_true,
+            diag=diag, q_stride=q_stride, has_win=window is not None,
+            win=window if window is not None else 0)
         return out, lse
-    return _eager_fp8(q8, k8, v8t, qs, ks, vs, sm_scale, causal, nk_true)
+    return _eager_fp8(q8, k8, v8t, qs, ks, vs, sm_scale, causal, nk_true,
+                      diag, q_stride, window)
 
 
 def _dequant(x8: Tensor, scales: Tensor) -> Tensor:
@@ -135,9 +163,11 @@ def _dequant(x8: Tensor, scales: Tensor) -> Tensor:
             * torch.exp2(scales.float() - 127.0).repeat_interleave(64, dim=-1))
 
 
-def _eager_fp8(q8, k8, v8t, qs, ks, vs, sm_scale, causal, nk_true):
+def _eager_fp8(q8, k8, v8t, qs, ks, vs, sm_scale, causal, nk_true,
+               diag=0, q_stride=1, window=None):
     """CPU fallback: dequantized eager attention with the kernel's masking
-    semantics (true-length + causal).  Approximates the GPU path to within
+    semantics (true length, causal at qpos(i) = i * q_stride + diag, window;
+    rows with no key: out 0, lse LSE_FLOOR).  Approximates the GPU path to within
     its P-quantization error (the fallback keeps P in fp32) — it exists so
     the fp8 wrapper/ring logic runs and tests anywhere, like the rest of
     the framework's CPU fallbacks."""
@@ -158,11 +188,14 @@ def _eager_fp8(q8, k8, v8t, qs, ks, vs, sm_scale, causal, nk_true):
     sim = torch.einsum("bihd,bjhd->bhij", qd, kd) * sm_scale
     jpos = torch.arange(nk, device=sim.device)
     sim = sim.masked_fill((jpos >= nk_true)[None, None, None, :], float("-inf"))
+    qpos = torch.arange(nq, device=sim.device) * q_stride + diag
     if causal:
-        ipos = torch.arange(nq, device=sim.device)
-        sim = sim.masked_fill((jpos[None, :] > ipos[:, None])[None, None],
+        sim = sim.masked_fill((jpos[None, :] > qpos[:, None])[None, None],
                               float("-inf"))
-    lse = sim.logsumexp(dim=-1)                            # (b, h, nq)
+    if window is not None:
+        sim = sim.masked_fill(((qpos[:, None] - jpos[None, :]) > window)[None, None],
+                              float("-inf"))
+    lse = sim.logsumexp(dim=-1).clamp(min=LSE_FLOOR)       # (b, h, nq)
     out = torch.einsum("bhij,bjhd->bihd", torch.softmax(sim, dim=-1), vd)
     out = torch.nan_to_num(out)                            # all-masked rows
     return out.to(torch.bfloat16), lse.float()
@@ -187,6 +220,8 @@ def ring_flash_attn_fp8(
     sm_scale: float | None = None,
     ring_size: int | None = None,
     causal: bool = False,
+    striped: bool = False,
+    max_lookback_seq_len: int | None = None,
 ) -> tuple[Tensor, Tensor]:
     """RING attention forward in MX-FP8 over sharded KV.
 
@@ -196,41 +231,52 @@ def ring_flash_attn_fp8(
     the transport time too) — and every hop's fused-fp8 partial merges by
     logsumexp (exact online-softmax combine in fp32).
 
-    Causal (rank-ordered shards, rank r owning global rows
-    [r*n_shard, (r+1)*n_shard)): a hop whose source ring-rank is ahead of
-    this rank contributes nothing and skips the kernel entirely; the
-    diagonal hop (source == self) runs the causal fp8 kernel; earlier
-    sources run the full non-causal kernel.  Striped/zig-zag layouts stay
-    on the bf16 ring path.
+    Causal: every hop takes its mask from `_hop_geometry`, the bf16 ring's
+    own (q rank, kv rank) -> (skip, diag, win) rule, with n_shard the TRUE
+    shard length.  Rank-ordered shards (rank r owns global rows
+    [r*n_shard, (r+1)*n_shard)) skip hops from later ranks, cut the own hop
+    at the diagonal and run earlier ones full.  `striped=True` (rank r owns
+    rows r, r + R, ...; requires causal) makes every hop a triangle with
+    diag 0 (source <= self) or -1, so every rank does the same work.
+    `max_lookback_seq_len` adds the sliding window in global positions and
+    skips hops beyond it.  A skipped hop launches nothing; rows a hop masks
+    whole merge as out 0 / lse LSE_FLOOR.  Zig-zag stays on the bf16 path.
 
     Returns (out bf16 (b, n, h, d), lse fp32 (b, h, n)).
     """
     from ..parallel import RingTopology, all_ring_pass, is_distributed
     from ..parallel.ring_pass import null_ring_pass
+    from .ring_flash_hip import _hop_geometry
 
+    assert causal or not striped, "striped ring attention requires causal"
+    lookback = max_lookback_seq_len
+    assert causal or lookback is None, "lookback (sliding window) requires causal"
     sm = sm_scale if sm_scale is not None else q.shape[-1] ** -0.5
+    n_shard = k.shape[1]
     q8, k8, v8t, qs, ks, vs = quantize_fp8(q, k, v)
 
-    my_rank = 0
+    my_rank, ring = 0, 1
     if is_distributed():
         topo = RingTopology(ring_size)
-        my_rank = topo.ring_rank
+        my_rank, ring = topo.ring_rank, topo.ring_size
         hops = all_ring_pass(topo, k8, v8t, ks, vs)
     else:
         hops = null_ring_pass(k8, v8t, ks, vs)
 
     out = lse = None
     for info, (k8h, v8th, ksh, vsh) in hops:
-        src = info.source_ring_rank
-        if causal and src > my_rank:
-            continue                                  # strictly future rows
+        skip, diag, win = _hop_geometry(my_rank, info.source_ring_rank, n_shard,
+                                        ring, striped, causal, lookback)
+        if skip:
+            continue                   # future rows, or beyond the window
         o_h, l_h = flash_attn_fp8_quantized(
-            q8, k8h, v8th, qs, ksh, vsh, sm,
-            causal=causal and src == my_rank, nk_true=k.shape[1])
+            q8, k8h, v8th, qs, ksh, vsh, sm, causal=causal, nk_true=n_shard,
+            diag=diag, window=win if lookback is not None else None)
         if out is None:
             out, lse = o_h.float(), l_h
         else:
             out, lse = merge_fp8_partials(out, lse, o_h, l_h)
+    assert out is not None, "every hop masked: degenerate configuration"
     nq = q.shape[1]
     return out[:, :nq].to(q.dtype), lse[..., :nq]
 
