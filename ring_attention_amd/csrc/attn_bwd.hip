@@ -13,7 +13,9 @@
 //    element (each q row is owned by exactly one workgroup).
 //  * attn_bwd_dkv_kernel — COLUMN-parallel: each wave owns 32 kv rows with
 //    K/V fragments in registers across the whole q loop; Q/dO stream through
-//    LDS (row-major + pair-staged transpose); p/ds fragments are built
+//    LDS (one row-major image each, read row-wise for S/dP and through
+//    ds_read_b64_tr_b16 for dv/dk; d128: row-major + pair-staged
+//    transpose); p/ds fragments are built
 //    in-register (lane = kv); dk/dv accumulate in registers and are written
 //    once.  GQA: the group's query heads are iterated with K/V resident, so
 //    dk/dv need no cross-head reduction.
@@ -236,9 +238,11 @@ void attn_bwd_dq_kernel(BwdParams p) { // cap 256 VGPR, stop the 220 B/thread
                         }
                         float pv = __builtin_amdgcn_exp2f(SOFTCLAMP ? x - lse_i : x);
                         // the uniform softmax scale is applied once to the
-                        // fp32 accumulators in the epilogue
-                        dse[e] = pv * (dp[r] - delta_i);
-                        if constexpr (SOFTCLAMP) dse[e] *= dtanh;
+                        // fp32 accumulators in the epilogue.  sub_f32 /
+                        // mul_f32: single-issue, never v_pk_*_f32 beside
+                        // the MFMAs (attn_common.h)
+                        dse[e] = mul_f32(pv, sub_f32(dp[r], delta_i));
+                        if constexpr (SOFTCLAMP) dse[e] = mul_f32(dse[e], dtanh);
                     }
                     pk[kb * 8 + x2] = pack_bf16x2(dse[0], dse[1]);
                 }
@@ -272,8 +276,8 @@ void attn_bwd_dq_kernel(BwdParams p) { // cap 256 VGPR, stop the 220 B/thread
                         if (P.kmask) ok = ok && lds.kmask[par][jj - j0];
                         float pv = ok ? __builtin_amdgcn_exp2f(
                             SOFTCLAMP ? x - lse_i : x - lse_i) : 0.f;
-                        dse[e] = pv * (dp[r] - delta_i);
-                        if constexpr (SOFTCLAMP) dse[e] *= dtanh;
+                        dse[e] = mul_f32(pv, sub_f32(dp[r], delta_i));
+                        if constexpr (SOFTCLAMP) dse[e] = mul_f32(dse[e], dtanh);
                     }
                     pk[kb * 8 + x2] = pack_bf16x2(dse[0], dse[1]);
                 }
@@ -345,7 +349,9 @@ void attn_bwd_dq_kernel(BwdParams p) { // cap 256 VGPR, stop the 220 B/thread
     // loop: apply it once to this launch's finished fp32 partial, ahead of
     // every output mode (exact for power-of-two scales)
     #pragma unroll
-    for (int db = 0; db < DBLK; ++db) dq_acc[db] *= P.scale;
+    for (int db = 0; db < DBLK; ++db)
+        #pragma unroll
+        for (int r = 0; r < 16; ++r) dq_acc[db][r] = mul_f32(dq_acc[db][r], P.scale);
     if (P.dq_bf) {
         // fused epilogue (single-pass only, enforced by the binding): this
         // lane is the unique writer of its row, so round the finished fp32
@@ -389,7 +395,11 @@ void attn_bwd_dq_kernel(BwdParams p) { // cap 256 VGPR, stop the 220 B/thread
 static constexpr int KVROWS_WAVE = 32;   // 8 waves own the ROWS_WG kv rows
 static_assert(ROWS_WG == 8 * KVROWS_WAVE);
 
-template <int D, int QT>
+// SINGLE_IMAGE (d32, d64): Q and dO are staged once, row-major; the dv/dk
+// MFMAs take their transposed operands from the same images with
+// ds_read_b64_tr_b16 (as dq takes K^T from its k image).  d128 keeps the
+// second, pair-staged transposed pair of images.
+template <int D, int QT, bool SINGLE_IMAGE>
 struct DkvLds {
     // double-buffered q-tile images (one barrier per q tile; staging writes
     // and next-next tile's loads overlap the MFMAs, as in the forward kernel)
@@ -401,6 +411,28 @@ struct DkvLds {
     __align__(16) float delta[2][QT];
 };
 
+template <int D, int QT>
+struct DkvLds<D, QT, true> {
+    __align__(16) __bf16 q[2][QT * D];      // [q][d]   swizzled rows
+    __align__(16) __bf16 do_[2][QT * D];    // [q][d]
+    __align__(16) float lse[2][QT];
+    __align__(16) float delta[2][QT];
+    // the bf16 epilogue stages 2 x ROWS_WG x D values through this
+    // allocation, more than the images take: the difference stays allocated
+    // (registers, not LDS, hold occupancy at one workgroup per CU)
+    __align__(16) __bf16 epilogue_room[2 * ROWS_WG * D - 4 * QT * D];
+    static_assert(2 * ROWS_WG * D > 4 * QT * D);
+};
+
+
+// staging registers of the transposed images' row pairs: the two-image form
+// has them, the single-image form has none
+template <int TREGS, bool TWO_IMAGE>
+struct DkvTrStage {
+    bf16x8 q_a[TREGS], q_b[TREGS], do_a[TREGS], do_b[TREGS];
+};
+template <int TREGS>
+struct DkvTrStage<TREGS, false> {};
 
 template <int D, int QT, bool SOFTCLAMP, bool PAIRED, bool BIAS = false>
 __global__ __launch_bounds__(512, 2)   // see dq kernel note (552 B spills)
@@ -411,7 +443,10 @@ void attn_bwd_dkv_kernel(BwdParams p) {
     constexpr int QBLKS = QT / 32;
     constexpr int TM = (QT / 8 - 1) < 7 ? (QT / 8 - 1) : 7;
 
-    __shared__ DkvLds<D, QT> lds;
+    // d32 / d64 stage one row-major image per operand (see DkvLds); d128 has
+    // not been measured in that form and keeps two
+    constexpr bool SINGLE_IMAGE = (D != 128);
+    __shared__ DkvLds<D, QT, SINGLE_IMAGE> lds;
 
     // the d64 body runs in a noinline frame (see the call below) and keeps
     // its wave-uniform state in SGPRs: it captures nothing
@@ -523,7 +558,7 @@ void attn_bwd_dkv_kernel(BwdParams p) {
         constexpr int TPAIRS = (QT / 2) * (D / 8);
         constexpr int TREGS = (TPAIRS + 511) / 512;
         uint4 qst[QREGS], dost[QREGS];
-        bf16x8 qtv_a[TREGS], qtv_b[TREGS], dov_a[TREGS], dov_b[TREGS];
+        DkvTrStage<TREGS, !SINGLE_IMAGE> trs;
         float lse_st = 0.f, delta_st = 0.f;
         long t_next = t0;
 
@@ -563,18 +598,20 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                     dost[r] = ld16(dotile, off);
                 }
             }
-            #pragma unroll
-            for (int r = 0; r < TREGS; ++r) {
-                int c = tid + r * 512;
-                if (c < TPAIRS) {
-                    int jp = c % (QT / 2);
-                    int d0 = (c / (QT / 2)) * 8;
-                    unsigned offa = (unsigned)min(jp * 2, last) * qrow_bytes + d0 * 2;
-                    unsigned offb = (unsigned)min(jp * 2 + 1, last) * qrow_bytes + d0 * 2;
-                    qtv_a[r] = ld8h(qtile, offa);
-                    qtv_b[r] = ld8h(qtile, offb);
-                    dov_a[r] = ld8h(dotile, offa);
-                    dov_b[r] = ld8h(dotile, offb);
+            if constexpr (!SINGLE_IMAGE) {
+                #pragma unroll
+                for (int r = 0; r < TREGS; ++r) {
+                    int c = tid + r * 512;
+                    if (c < TPAIRS) {
+                        int jp = c % (QT / 2);
+                        int d0 = (c / (QT / 2)) * 8;
+                        unsigned offa = (unsigned)min(jp * 2, last) * qrow_bytes + d0 * 2;
+                        unsigned offb = (unsigned)min(jp * 2 + 1, last) * qrow_bytes + d0 * 2;
+                        trs.q_a[r] = ld8h(qtile, offa);
+                        trs.q_b[r] = ld8h(qtile, offb);
+                        trs.do_a[r] = ld8h(dotile, offa);
+                        trs.do_b[r] = ld8h(dotile, offb);
+                    }
                 }
             }
             if (tid < QT) {
@@ -595,11 +632,13 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                         qst[r] = uint4{0, 0, 0, 0};
                         dost[r] = uint4{0, 0, 0, 0};
                     }
-                #pragma unroll
-                for (int r = 0; r < TREGS; ++r) {
-                    int la = ((tid + r * 512) % (QT / 2)) * 2;
-                    if (la >= rows) { qtv_a[r] = bf16x8{}; dov_a[r] = bf16x8{}; }
-                    if (la + 1 >= rows) { qtv_b[r] = bf16x8{}; dov_b[r] = bf16x8{}; }
+                if constexpr (!SINGLE_IMAGE) {
+                    #pragma unroll
+                    for (int r = 0; r < TREGS; ++r) {
+                        int la = ((tid + r * 512) % (QT / 2)) * 2;
+                        if (la >= rows) { trs.q_a[r] = bf16x8{}; trs.do_a[r] = bf16x8{}; }
+                        if (la + 1 >= rows) { trs.q_b[r] = bf16x8{}; trs.do_b[r] = bf16x8{}; }
+                    }
                 }
             }
             #pragma unroll
@@ -611,32 +650,34 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                     *(uint4*)(lds.do_[par] + row * D + swz<D / 8>(row, ch) * 8) = dost[r];
                 }
             }
-            #pragma unroll
-            for (int r = 0; r < TREGS; ++r) {
-                int c = tid + r * 512;
-                if (c < TPAIRS) {
-                    // q pairs land in the dv/dk k order (kperm_pair): the
-                    // packed p/ds pairs are then the fragments as they stand
-                    int jp = kperm_pair(c % (QT / 2));
-                    int d0 = (c / (QT / 2)) * 8;
-                    // element (d0 + e, pair jp) sits at byte
-                    //   (d0 + e) * QT * 2 + ((jp * 4) ^ (((d0 + e) & TM) << 4))
-                    // of image `par`.  d0 % 8 == 0, so the swizzle term is
-                    // (e & TM) << 4; it is below the QT * 2 row size and the
-                    // buffer and row-group offsets have those bits clear, so
-                    // the XOR applies to the whole address: one base
-                    // register and one v_xor per store instead of eight
-                    // loop-invariant addresses held (and spilled) across
-                    // the tile loop
-                    static_assert((TM << 4) < QT * 2 && (D * QT * 2) % (QT * 2) == 0);
-                    const unsigned base = par * (D * QT * 2) + d0 * QT * 2 + jp * 4;
-                    #pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        unsigned byte_off = (base ^ ((e & TM) << 4)) + e * QT * 2;
-                        __bf16 pq[2] = {qtv_a[r][e], qtv_b[r][e]};
-                        __bf16 pd[2] = {dov_a[r][e], dov_b[r][e]};
-                        *(uint32_t*)((char*)lds.qt[0] + byte_off) = *(uint32_t*)pq;
-                        *(uint32_t*)((char*)lds.dot[0] + byte_off) = *(uint32_t*)pd;
+            if constexpr (!SINGLE_IMAGE) {
+                #pragma unroll
+                for (int r = 0; r < TREGS; ++r) {
+                    int c = tid + r * 512;
+                    if (c < TPAIRS) {
+                        // q pairs land in the dv/dk k order (kperm_pair): the
+                        // packed p/ds pairs are then the fragments as they stand
+                        int jp = kperm_pair(c % (QT / 2));
+                        int d0 = (c / (QT / 2)) * 8;
+                        // element (d0 + e, pair jp) sits at byte
+                        //   (d0 + e) * QT * 2 + ((jp * 4) ^ (((d0 + e) & TM) << 4))
+                        // of image `par`.  d0 % 8 == 0, so the swizzle term is
+                        // (e & TM) << 4; it is below the QT * 2 row size and the
+                        // buffer and row-group offsets have those bits clear, so
+                        // the XOR applies to the whole address: one base
+                        // register and one v_xor per store instead of eight
+                        // loop-invariant addresses held (and spilled) across
+                        // the tile loop
+                        static_assert((TM << 4) < QT * 2 && (D * QT * 2) % (QT * 2) == 0);
+                        const unsigned base = par * (D * QT * 2) + d0 * QT * 2 + jp * 4;
+                        #pragma unroll
+                        for (int e = 0; e < 8; ++e) {
+                            unsigned byte_off = (base ^ ((e & TM) << 4)) + e * QT * 2;
+                            __bf16 pq[2] = {trs.q_a[r][e], trs.q_b[r][e]};
+                            __bf16 pd[2] = {trs.do_a[r][e], trs.do_b[r][e]};
+                            *(uint32_t*)((char*)lds.qt[0] + byte_off) = *(uint32_t*)pq;
+                            *(uint32_t*)((char*)lds.dot[0] + byte_off) = *(uint32_t*)pd;
+                        }
                     }
                 }
             }
@@ -665,8 +706,9 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                 !P.kmask;
 
             // MFMA operand fragments of one 32-row q block: the S/dP pair
-            // (rows of the q / dO images) and the dv/dk pair (rows of the
-            // transposed images)
+            // (rows of the q / dO images) and the dv/dk pair (SINGLE_IMAGE:
+            // columns of the same images, read transposed; else rows of
+            // the transposed images)
             bf16x8 qa[KSTEPS], da[KSTEPS], doa[2 * DBLK], qta[2 * DBLK];
             auto read_sdp = [&](int qb) {
                 #pragma unroll
@@ -677,19 +719,63 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                     da[ks] = *(const bf16x8*)(lds.do_[par] + qrow * D + swz<D / 8>(qrow, chunk) * 8);
                 }
             };
-            auto read_dvdk = [&](int qb) {
+            // SINGLE_IMAGE: dO^T / Q^T fragments straight from the row-major
+            // images.  Fragment db*2+half holds, for d column db*32 + l31,
+            // q rows qb*32 + 16*half + 4*lhi + {0,1,2,3, 8,9,10,11} (the k
+            // order of the packed p/ds pairs, kperm_pair): two transposed
+            // reads of 4 consecutive rows, u = 0, 1.  Lane f = lane & 15 of
+            // each 16-lane group g16 addresses row + (f >> 2), columns
+            // db*32 + 16*g16 + 4*(f & 3) .. +4, and the hardware delivers
+            // out[l][e] = image[row + e][db*32 + (l & 31)].  Every row
+            // term but 4*lhi + (f >> 2) is a multiple of 8, so the swizzle
+            // key (row & 7) is per lane and each read is a per-lane base
+            // plus a compile-time offset (the base of db 1 is db 0's with
+            // the 64-byte bit flipped).
+            auto read_dvdk_tr = [&](int qb) {
+                typedef __attribute__((address_space(3))) bf16x4* lds_v4;
+                const int f15 = lane & 15;
+                const int g16 = (lane >> 4) & 1;
+                const int lrow = 4 * lhi + (f15 >> 2);
+                const int key = lrow & (D / 8 < 8 ? D / 8 - 1 : 7);
                 #pragma unroll
-                for (int db = 0; db < DBLK; ++db)
+                for (int db = 0; db < DBLK; ++db) {
+                    const int col = db * 32 + 16 * g16 + 4 * (f15 & 3);
+                    const int lane_off = lrow * D + ((col / 8) ^ key) * 8 + (col % 8);
                     #pragma unroll
                     for (int half = 0; half < 2; ++half) {
-                        int qk = qb * 2 + half;
-                        int drow = db * 32 + l31;
-                        int ch = qk * 2 + lhi;
-                        doa[db * 2 + half] = *(const bf16x8*)(lds.dot[par] + drow * QT +
-                                                              ((ch ^ (drow & TM))) * 8);
-                        qta[db * 2 + half] = *(const bf16x8*)(lds.qt[par] + drow * QT +
-                                                              ((ch ^ (drow & TM))) * 8);
+                        bf16x4 dv4[2], qv4[2];
+                        #pragma unroll
+                        for (int u = 0; u < 2; ++u) {
+                            const int off = (qb * 32 + 16 * half + 8 * u) * D + lane_off;
+                            dv4[u] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+                                (lds_v4)(lds.do_[par] + off));
+                            qv4[u] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
+                                (lds_v4)(lds.q[par] + off));
+                        }
+                        doa[db * 2 + half] = __builtin_shufflevector(
+                            dv4[0], dv4[1], 0, 1, 2, 3, 4, 5, 6, 7);
+                        qta[db * 2 + half] = __builtin_shufflevector(
+                            qv4[0], qv4[1], 0, 1, 2, 3, 4, 5, 6, 7);
                     }
+                }
+            };
+            auto read_dvdk = [&](int qb) {
+                if constexpr (SINGLE_IMAGE) {
+                    read_dvdk_tr(qb);
+                } else {
+                    #pragma unroll
+                    for (int db = 0; db < DBLK; ++db)
+                        #pragma unroll
+                        for (int half = 0; half < 2; ++half) {
+                            int qk = qb * 2 + half;
+                            int drow = db * 32 + l31;
+                            int ch = qk * 2 + lhi;
+                            doa[db * 2 + half] = *(const bf16x8*)(lds.dot[par] + drow * QT +
+                                                                  ((ch ^ (drow & TM))) * 8);
+                            qta[db * 2 + half] = *(const bf16x8*)(lds.qt[par] + drow * QT +
+                                                                  ((ch ^ (drow & TM))) * 8);
+                        }
+                }
             };
 
             // masked path: the lane's half offset and its one 64-bit q
@@ -779,8 +865,8 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                             pe[e] = pv;
                             // the uniform softmax scale is applied once to
                             // dk's fp32 accumulators in the epilogue
-                            dse[e] = pv * (dp[r] - delta4[r & 3]);
-                            if constexpr (SOFTCLAMP) dse[e] *= dtanh;
+                            dse[e] = mul_f32(pv, sub_f32(dp[r], delta4[r & 3]));
+                            if constexpr (SOFTCLAMP) dse[e] = mul_f32(dse[e], dtanh);
                         }
                         p_pk[x2] = pack_bf16x2(pe[0], pe[1]);
                         ds_pk[x2] = pack_bf16x2(dse[0], dse[1]);
@@ -836,8 +922,8 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                             if (P.kmask) ok = ok && kmask_own;
                             float pv = ok ? __builtin_amdgcn_exp2f(x - lse4[r & 3]) : 0.f;
                             pe[e] = pv;
-                            dse[e] = pv * (dp[r] - delta4[r & 3]);
-                            if constexpr (SOFTCLAMP) dse[e] *= dtanh;
+                            dse[e] = mul_f32(pv, sub_f32(dp[r], delta4[r & 3]));
+                            if constexpr (SOFTCLAMP) dse[e] = mul_f32(dse[e], dtanh);
                         }
                         p_pk[x2] = pack_bf16x2(pe[0], pe[1]);
                         ds_pk[x2] = pack_bf16x2(dse[0], dse[1]);
@@ -847,8 +933,10 @@ void attn_bwd_dkv_kernel(BwdParams p) {
                 // dv^T[d][kv] += dO^T x p ; dk[kv][d] += ds^T x Q^T-read.
                 // p_pk/ds_pk[4*half .. 4*half+3] (lane = kv) are the
                 // fragments of k-step `half` as packed: q rows
-                // 16*half + 4*lhi + {0,1,2,3,8,9,10,11}, the order the
-                // qt/dot images are staged in (kperm_pair)
+                // 16*half + 4*lhi + {0,1,2,3,8,9,10,11}: the rows the
+                // transposed reads pick (read_dvdk_tr) and the order the
+                // qt/dot images of the two-image form are staged in
+                // (kperm_pair)
                 if constexpr (PREFETCH) {
                     if (qb + 1 < QBLKS) {
                         read_sdp(qb + 1);
@@ -874,7 +962,9 @@ void attn_bwd_dkv_kernel(BwdParams p) {
     // loop: apply it once to this launch's finished fp32 dk partial, ahead
     // of every output mode (exact for power-of-two scales)
     #pragma unroll
-    for (int db = 0; db < DBLK; ++db) dk_acc[db] *= P.scale;
+    for (int db = 0; db < DBLK; ++db)
+        #pragma unroll
+        for (int r = 0; r < 16; ++r) dk_acc[db][r] = mul_f32(dk_acc[db][r], P.scale);
 
     if (P.dk_bf) {
         // fused epilogue (single-pass only, enforced by the binding): this
@@ -892,7 +982,7 @@ void attn_bwd_dkv_kernel(BwdParams p) {
         constexpr int ECH = D / 8;
         __bf16* stg_dk = (__bf16*)&lds;
         __bf16* stg_dv = stg_dk + ROWS_WG * D;
-        static_assert(sizeof(DkvLds<D, QT>) >= 2 * ROWS_WG * D * sizeof(__bf16));
+        static_assert(sizeof(DkvLds<D, QT, SINGLE_IMAGE>) >= 2 * ROWS_WG * D * sizeof(__bf16));
         const int wrow0 = wid * KVROWS_WAVE;
         const long orow_stride = (long)P.hk * D;
         __bf16* dkb = (__bf16*)P.dk_bf + ((long)b * P.nk) * orow_stride + (long)hkh * D;

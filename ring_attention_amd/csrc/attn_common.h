@@ -54,6 +54,34 @@ __device__ __forceinline__ int swz(int row, int chunk) {
     return chunk ^ (row & (CH < 8 ? CH - 1 : 7));
 }
 
+// Single-issue f32 subtract / multiply for the softmax and ds blocks of the
+// backward tile loops.  Written in C++, neighbouring register pairs of these
+// ops are SLP-packed into v_pk_add_f32 / v_pk_mul_f32 under plain -O3, and a
+// packed f32 op issued beside MFMAs costs more than the two scalar ops it
+// replaces.  The helpers are the same IEEE operation per element (bitwise
+// equal results): the op itself stays C++ and its RESULT passes through an
+// empty asm, which the vectorizer cannot look through, so no pair of them
+// is ever joined.  Not volatile and no clobbers: the scheduler places them
+// like any other VALU op.
+// The op must NOT be written as asm ("v_sub_f32 %0, %1, %2"): these operands
+// are MFMA results, the wait states between an MFMA and a VALU read of its
+// result are inserted by the compiler, and it inserts none in front of
+// inline asm.  That form read accumulators ahead of the MFMA's write (dq
+// wrong by orders of magnitude on the GPU).
+// (-fno-slp-vectorize for the translation unit was the alternative: it also
+// changes staging and epilogue code, moves scratch up in four
+// instantiations, and leaves the vector-typed epilogue scaling packed.)
+__device__ __forceinline__ float sub_f32(float a, float b) {
+    float r = a - b;
+    asm("" : "+v"(r));
+    return r;
+}
+__device__ __forceinline__ float mul_f32(float a, float b) {
+    float r = a * b;
+    asm("" : "+v"(r));
+    return r;
+}
+
 // fast tanh from builtins: tanh(x) = 1 - 2/(exp2(2x*log2e) + 1); avoids the
 // libm tanhf whose inlined body injects v_div_* sequences into the hot loop
 __device__ __forceinline__ float fast_tanhf(float x) {
