@@ -21,6 +21,13 @@ Works with and without `--fp8` (fused quantising append), on GPU and CPU.
 In a single process the ragged prompts first go through `paged_prefill_attn`
 right after the prompt append: causal attention straight off the pages, one
 length and one diagonal per sequence.
+
+`--paged --window W` serves a sliding-window (lookback) model: the prefill and
+every decode step attend only the W keys behind each query, ranks that do not
+hold the tail tell the kernel how many keys the later ranks hold
+(`kv_after`), and after every step `release_prefix` hands the pages that fell
+out of the window back to the pool — the cache holds about W / page_size + 2
+pages per sequence however long the sequence grows.
 """
 
 from __future__ import annotations
@@ -54,7 +61,12 @@ def main():
                          "one token per step")
     ap.add_argument("--page-size", type=int, default=64,
                     help="tokens per page with --paged (power of two, 16..256)")
+    ap.add_argument("--window", type=int, default=None,
+                    help="with --paged: token-exact lookback window; pages "
+                         "that fall out of it are released after every step")
     args = ap.parse_args()
+    if args.window is not None and not args.paged:
+        ap.error("--window needs --paged")
     if args.batch is None:
         args.batch = 4 if args.paged else 1
 
@@ -159,7 +171,8 @@ def serve_paged(args, rank, world, device, dtype):
         torch.manual_seed(11)
         q_prompt = torch.randn(b, t, h, d, device=device, dtype=dtype)
         t0 = time.perf_counter()
-        o_prompt = paged_prefill_attn(q_prompt, cache, local, causal=True)
+        o_prompt = paged_prefill_attn(q_prompt, cache, local, causal=True,
+                                      window=args.window)
         if device == "cuda":
             torch.cuda.synchronize()
         dt = time.perf_counter() - t0
@@ -178,7 +191,18 @@ def serve_paged(args, rank, world, device, dtype):
         # every rank decodes over its shard: 2 collective rounds per token
         if tail:
             cache.append(q, q.flip(-1))
-        out = tree_attn_decode_paged(q, cache)
+        if args.window is None:
+            out = tree_attn_decode_paged(q, cache)
+        else:
+            # the query is the sequence's last token, step + 1 tokens past the
+            # prompt on the tail rank: every other rank passes what the later
+            # ranks hold, and every rank gives back the pages that the NEXT
+            # query (one position on) can no longer reach
+            total = [n + step + 1 for n in lens]
+            after = None if tail else [n - e for n, e in zip(total, hi)]
+            out = tree_attn_decode_paged(q, cache, window=args.window, kv_after=after)
+            cache.release_prefix([max(0, n - args.window - s)
+                                  for n, s in zip(total, lo)])
         outs.append(out)
         q = out
     if device == "cuda":
@@ -186,7 +210,9 @@ def serve_paged(args, rank, world, device, dtype):
     dt = (time.perf_counter() - t0) / args.steps
 
     if rank == 0:
-        print(f"world {world}  paged{' fp8' if args.fp8 else ''}  page {ps}  "
+        win = "" if args.window is None else f"  window {args.window}"
+        print(f"world {world}  paged{' fp8' if args.fp8 else ''}  page {ps}{win}  "
+              f"pages held {cache.pages_held()}{' on rank 0' if world > 1 else ''}  "
               f"batch {b}  kv {lens[0]}..{lens[-1]} (+{args.steps})  "
               f"{args.steps} steps  {dt*1e6:.0f} us/token  "
               f"out[0,0,0,:4] = {outs[-1][0,0,0,:4].float().tolist()}")

@@ -363,6 +363,12 @@ struct PagedDecodeParams {
     float scale;
     long chunks;            // kv-split S (0 = auto from max_seq_len)
     long max_seq_len;       // host-known upper bound of seq_lens
+    // lookback window: the query of row (b, iq) sits at position
+    // seq_len + kv_after[b] - nq + iq (local key coordinates) and attends
+    // keys [clamp(position - win, 0, limit), limit)
+    int has_win;            // 0 = no window (win and kv_after unused)
+    long win;               // >= 0
+    const int* kv_after;    // int32 (B): tokens held by LATER ranks, or null (0)
 };
 
 void launch_decode_partial_paged(const PagedDecodeParams& p, int head_dim, bool fp8,

@@ -513,12 +513,15 @@ std::vector<at::Tensor> decode_partial_paged(
     at::Tensor q, at::Tensor k_pages, at::Tensor v_pages,
     std::optional<at::Tensor> k_scales, std::optional<at::Tensor> v_scales,
     at::Tensor block_table, at::Tensor seq_lens, int64_t max_seq_len,
-    double sm_scale, bool causal, int64_t chunks_in) {
+    double sm_scale, bool causal, int64_t chunks_in,
+    bool has_win, int64_t win, std::optional<at::Tensor> kv_after) {
     // q bf16 (B,HQ,NQ,D); pages (P,HK,PS,D) bf16, or uint8 e4m3 with per-row
     // e8m0 scales (P,HK,PS) — the page dtype selects the fp8 kernel;
     // block_table int32 (B,max_pages), seq_lens int32 (B,).  max_seq_len is
     // the HOST's upper bound of seq_lens (drives the kv-split; no device
-    // read).  Same output contract as decode_partial.
+    // read).  Same output contract as decode_partial.  has_win / win: the
+    // token-exact lookback window; kv_after int32 (B,) = tokens of each
+    // sequence held by later ranks (None = 0).
     CHECK_BF16_CONTIG(q);
     TORCH_CHECK(q.dim() == 4, "q must be (B,HQ,NQ,D)");
     const int64_t B = q.size(0), H = q.size(1), NQ = q.size(2), D = q.size(3);
@@ -530,11 +533,22 @@ std::vector<at::Tensor> decode_partial_paged(
     TORCH_CHECK(max_seq_len >= 0
                 && max_seq_len <= block_table.size(1) * k_pages.size(2),
                 "max_seq_len exceeds what block_table can address");
+    TORCH_CHECK(!has_win || (win >= 0 && win < (int64_t(1) << 40)),
+                "win must lie in [0, 2^40)");
+    if (has_win && kv_after.has_value()) {
+        TORCH_CHECK(kv_after->scalar_type() == at::kInt && kv_after->is_contiguous()
+                    && kv_after->dim() == 1 && kv_after->size(0) == B
+                    && kv_after->device() == q.device(),
+                    "kv_after must be contiguous int32 (B,) on q's device");
+    }
     int64_t waves = B * H * NQ;
     // the dense bindings' swept kv-split heuristic (~512 keys per wave,
-    // waves capped near 8192, S <= 256) on the longest sequence
+    // waves capped near 8192, S <= 256) on the longest sequence, or with a
+    // window on the longest row span (launch_decode_partial_paged)
+    const int64_t span = has_win ? std::min<int64_t>(max_seq_len, win + NQ + 63)
+                                 : max_seq_len;
     int64_t chunks = chunks_in > 0 ? chunks_in : std::max<int64_t>(
-        1, std::min<int64_t>(std::min<int64_t>(max_seq_len / 512 + 1, 256),
+        1, std::min<int64_t>(std::min<int64_t>(span / 512 + 1, 256),
                              8192 / std::max<int64_t>(waves, 1)));
     TORCH_CHECK(chunks <= 65535, "chunks must fit grid.y");
     TORCH_CHECK((waves + 3) / 4 * chunks < (int64_t(1) << 31), "grid too large");
@@ -564,6 +578,9 @@ std::vector<at::Tensor> decode_partial_paged(
     p.scale = sm_scale > 0 ? (float)sm_scale : (float)(1.0 / std::sqrt((double)D));
     p.chunks = chunks;
     p.max_seq_len = max_seq_len;
+    p.has_win = has_win ? 1 : 0;
+    p.win = has_win ? win : 0;
+    p.kv_after = has_win && kv_after.has_value() ? kv_after->data_ptr<int>() : nullptr;
     launch_decode_partial_paged(p, (int)D, fp8, at::hip::getCurrentHIPStream());
     TORCH_CHECK(hipGetLastError() == hipSuccess, "paged decode launch failed");
     return {out, lse};
@@ -731,7 +748,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::arg("k_scales"), py::arg("v_scales"), py::arg("block_table"),
             py::arg("seq_lens"), py::arg("max_seq_len"),
             py::arg("sm_scale") = -1.0, py::arg("causal") = false,
-            py::arg("chunks") = 0);
+            py::arg("chunks") = 0, py::arg("has_win") = false,
+            py::arg("win") = 0, py::arg("kv_after") = py::none());
     mod.def("paged_kv_append", &ring_attn::paged_kv_append,
             "write new tokens into a paged KV cache (fused fp8 quantisation)",
             py::arg("k_new"), py::arg("v_new"), py::arg("k_pages"),

@@ -20,7 +20,7 @@ namespace ring_attn {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-template <int D, bool FP8>
+template <int D, bool FP8, bool WIN>
 __global__ __launch_bounds__(256) void decode_partial_paged_kernel(PagedDecodeParams p) {
     // one wave per (b, q-head, query token); 4 waves per block; grid.y is
     // the kv-split.  Same group-major wave->row mapping as decode.hip: the 4
@@ -59,15 +59,29 @@ __global__ __launch_bounds__(256) void decode_partial_paged_kernel(PagedDecodePa
     long limit = min((long)p.seq_lens[b], cap);
     if (p.causal) limit -= (p.nq - 1 - iq);
     limit = max(limit, 0L);
-    // kv-split of THIS row's [0, limit): a slice of the batch-wide max range
-    // would leave short sequences on chunk 0 only.  The per-chunk span is
-    // rounded up to 64 keys so every loop pass of the wave starts 64-aligned
-    // (for page_size >= 64 its 64 keys then share one page).  Chunks past
-    // the row's end are empty and still write their partial below.
-    long per = (limit + gridDim.y - 1) / gridDim.y;
+    // lookback window (WIN): the row's query sits at position
+    // seq_len + kv_after - nq + iq in local key coordinates (kv_after =
+    // tokens of the sequence held by later ranks) and attends only keys
+    // j >= position - win, so its span is [lo, limit).  The unwindowed
+    // instantiation keeps lo = base = 0 as constants.
+    long lo = 0;
+    if constexpr (WIN) {
+        const long len = min((long)p.seq_lens[b], cap);
+        const long after = p.kv_after ? (long)p.kv_after[b] : 0L;
+        lo = min(max(len + after - p.nq + iq - p.win, 0L), limit);
+    }
+    const long base = lo & ~63L;
+    // kv-split of THIS row's span: a slice of the batch-wide max range
+    // would leave short sequences on chunk 0 only.  The span is cut from
+    // its 64-aligned start and the per-chunk length is rounded up to 64 keys
+    // so every loop pass of the wave starts 64-aligned (for page_size >= 64
+    // its 64 keys then share one page).  Chunks past the row's end are
+    // empty and still write their partial below; so does a row whose span
+    // is empty (lo == limit), which touches neither the table nor the pool.
+    long per = (limit - base + gridDim.y - 1) / gridDim.y;
     per = (per + 63) & ~63L;
-    const long j_lo = chunk * per;
-    const long j_hi = min(limit, j_lo + per);
+    const long j_lo = base + chunk * per;
+    const long j_hi = (!WIN || lo < limit) ? min(limit, j_lo + per) : j_lo;
 
     const __bf16* qp = (const __bf16*)p.q + (((long)b * p.h + h) * p.nq + iq) * D;
     const int* bt = p.block_table + (long)b * p.max_pages;
@@ -88,15 +102,25 @@ __global__ __launch_bounds__(256) void decode_partial_paged_kernel(PagedDecodePa
     // is fetched before the current rows are consumed so the dependent
     // table -> row load chain overlaps the row math.  Table entries are read
     // only for j < limit, i.e. only valid entries are ever touched.
+    // Keys in [base, lo) fall in the row's FIRST pass only (every later pass
+    // starts at or beyond base + 64 > lo) and do no row math.  Their table
+    // entries differ by page size:
+    //   page_size < 64  such a key can sit in a released page (entry -1):
+    //                   a lane reads its entry only when lo <= j;
+    //   page_size >= 64 the pass lies in the page that holds lo, which the
+    //                   host guard keeps live, and the id comes from the
+    //                   first lane: the read is NOT predicated on lo (lane 0
+    //                   would otherwise hand -1 to the whole wave) and only
+    //                   the row math is masked.
     long j = j_lo + lane;
-    int pg = j < j_hi ? bt[j >> shift] : -1;
+    int pg = (j < j_hi && (!WIN || uniform_page || j >= lo)) ? bt[j >> shift] : -1;
     while (j < j_hi) {
         const long jn = j + 64;
         const int pg_next = jn < j_hi ? bt[jn >> shift] : -1;
         // page_size >= 64: the wave's 64 keys share the page -> scalar id
         if (uniform_page) pg = __builtin_amdgcn_readfirstlane(pg);
         // a page id outside the pool is never dereferenced
-        if ((unsigned)pg < (unsigned)p.num_pages) {
+        if ((unsigned)pg < (unsigned)p.num_pages && (!WIN || j >= lo)) {
             const long row = ((((long)pg * p.hk + hk) << shift) | (j & pmask));
             if constexpr (!FP8) {
                 const __bf16* krow = (const __bf16*)p.k_pages + row * D;
@@ -200,22 +224,38 @@ void launch_decode_partial_paged(const PagedDecodeParams& p, int head_dim, bool 
     int waves = p.b * p.h * p.nq;
     // same swept kv-split fallback as launch_decode_partial, driven by the
     // host-known longest sequence (no device read on the step path)
+    // with a window the longest ROW SPAN drives the split, not the longest
+    // sequence: win + 1 keys, nq - 1 more over the query tokens, up to 63 of
+    // alignment in front
+    const long span = p.has_win ? min(p.max_seq_len, p.win + p.nq + 63) : p.max_seq_len;
     long chunks = p.chunks > 0 ? p.chunks
-                 : max(1L, min(min((long)(p.max_seq_len / 512 + 1), 256L),
+                 : max(1L, min(min((long)(span / 512 + 1), 256L),
                                8192L / max((long)waves, 1L)));
     dim3 grid((waves + 3) / 4, (unsigned)chunks);
     dim3 block(256);
+    // the window is a template switch: the unwindowed instantiations keep
+    // the code they had before the window existed
+#define LAUNCH_PAGED_DECODE(D_, FP8_)                                              \
+    do {                                                                           \
+        if (p.has_win)                                                             \
+            hipLaunchKernelGGL((decode_partial_paged_kernel<D_, FP8_, true>),      \
+                               grid, block, 0, stream, p);                         \
+        else                                                                       \
+            hipLaunchKernelGGL((decode_partial_paged_kernel<D_, FP8_, false>),     \
+                               grid, block, 0, stream, p);                         \
+    } while (0)
     if (head_dim == 64 && !fp8) {
-        hipLaunchKernelGGL((decode_partial_paged_kernel<64, false>), grid, block, 0, stream, p);
+        LAUNCH_PAGED_DECODE(64, false);
     } else if (head_dim == 128 && !fp8) {
-        hipLaunchKernelGGL((decode_partial_paged_kernel<128, false>), grid, block, 0, stream, p);
+        LAUNCH_PAGED_DECODE(128, false);
     } else if (head_dim == 64) {
-        hipLaunchKernelGGL((decode_partial_paged_kernel<64, true>), grid, block, 0, stream, p);
+        LAUNCH_PAGED_DECODE(64, true);
     } else if (head_dim == 128) {
-        hipLaunchKernelGGL((decode_partial_paged_kernel<128, true>), grid, block, 0, stream, p);
+        LAUNCH_PAGED_DECODE(128, true);
     } else {
         __builtin_trap();
     }
+#undef LAUNCH_PAGED_DECODE
 }
 
 

@@ -20,6 +20,15 @@ stays `dim_head ** -0.5`.  The value dim equals the key dim on the paged path
 Page allocation is host-side: a free list plus a host mirror of the lengths
 and the table, so appending and decoding never read anything back from the
 device (no `.item()` on the step path).
+
+Sliding-window serving: `release_prefix(keep_from)` hands back the pages of a
+sequence that lie wholly below a position the caller will never attend again.
+Positions stay ABSOLUTE: key j keeps table slot j // page_size for life, a
+released slot holds -1, `append` continues at seq_len, and
+`max_pages_per_seq` still bounds the absolute length (a ring-indexed table
+that would reuse the released slots is out of scope).  `host_starts[s]` is the
+number of released tokens; the attention entry points refuse, on the host and
+before any launch, a call that would attend below it.
 """
 
 from __future__ import annotations
@@ -39,8 +48,9 @@ class PagedKVCache:
 
     append(k, v, lens) writes new tokens (HIP append kernel on GPU: a 16-byte
     row copy for bf16, fused per-row e8m0/e4m3 quantisation for fp8) and
-    advances the lengths; free(seq) returns a sequence's pages; gather(seq)
-    rebuilds a dense (k, v) for debugging and tests.
+    advances the lengths; free(seq) returns a sequence's pages;
+    release_prefix(keep_from) returns the pages below a lookback window;
+    gather(seq) rebuilds a dense (k, v) for debugging and tests.
     """
 
     def __init__(self, num_pages: int, page_size: int, kv_heads: int,
@@ -71,14 +81,22 @@ class PagedKVCache:
 
         # host-side allocator state: pages are handed out from the END of
         # the free list; _pages[s] mirrors the valid prefix of table row s
+        # (-1 in the slots release_prefix has freed, _starts[s] // page_size
+        # of them)
         self._free: list[int] = list(range(self.num_pages - 1, -1, -1))
         self._pages: list[list[int]] = [[] for _ in range(self.max_seqs)]
         self._lens: list[int] = [0] * self.max_seqs
+        self._starts: list[int] = [0] * self.max_seqs
 
     # ---- host-side views ------------------------------------------------
     @property
     def host_lens(self) -> list[int]:
         return list(self._lens)
+
+    @property
+    def host_starts(self) -> list[int]:
+        """Released tokens per sequence: keys below host_starts[s] are gone."""
+        return list(self._starts)
 
     @property
     def max_seq_len(self) -> int:
@@ -89,7 +107,13 @@ class PagedKVCache:
         return len(self._free)
 
     def pages_of(self, seq: int) -> list[int]:
+        """Page ids by table slot; a slot freed by release_prefix reads -1."""
         return list(self._pages[seq])
+
+    def pages_held(self, seq: int | None = None) -> int:
+        """Pages currently owned by `seq` (default: by all sequences)."""
+        rows = self._pages if seq is None else [self._pages[seq]]
+        return sum(pg >= 0 for row in rows for pg in row)
 
     # ---- construction helpers -------------------------------------------
     @classmethod
@@ -115,6 +139,7 @@ class PagedKVCache:
         self.k_scales, self.v_scales = k_scales, v_scales
         self.block_table, self.seq_lens = block_table, seq_lens
         self._lens = [int(x) for x in seq_lens.tolist()]
+        self._starts = [0] * len(self._lens)
         table = block_table.tolist()
         self._pages = [table[s][:-(-n // page_size)]
                        for s, n in enumerate(self._lens)]
@@ -238,26 +263,92 @@ class PagedKVCache:
             self.k_pages[pg_idx, :, row_idx] = kb
             self.v_pages[pg_idx, :, row_idx] = vb
 
+    def release_prefix(self, keep_from) -> int:
+        """Free the pages a lookback window has left behind.
+
+        `keep_from` is a host list (or int tensor, read on the host like
+        `append`'s lens) with one position per sequence: "no later call
+        attends keys below this".  Every page of sequence s whose rows all
+        lie below min(keep_from[s], seq_len) goes back to the free list and
+        its table slot is set to -1 (one index_copy_, like `append`'s new
+        pages); nothing is read from the device.  host_starts[s] becomes the
+        number of released tokens: a multiple of page_size that never
+        decreases and never exceeds keep_from[s].  Releasing the same prefix
+        again does nothing.  Returns the number of pages freed.
+
+        The table stays indexed by absolute position (no ring indexing):
+        released slots are not reused and max_pages_per_seq still bounds the
+        absolute length of a sequence.
+        """
+        if isinstance(keep_from, Tensor):
+            keep_from = keep_from.tolist()
+        keep = [int(x) for x in keep_from]
+        if len(keep) != self.max_seqs:
+            raise ValueError(f"release_prefix: keep_from has {len(keep)} entries, "
+                             f"the cache holds {self.max_seqs} sequences")
+        if any(x < 0 for x in keep):
+            raise ValueError("release_prefix: keep_from must be >= 0")
+        ps = self.page_size
+        flat_idx = []
+        for s in range(self.max_seqs):
+            start = min(keep[s], self._lens[s]) // ps * ps
+            for slot in range(self._starts[s] // ps, start // ps):
+                self._free.append(self._pages[s][slot])
+                self._pages[s][slot] = -1
+                flat_idx.append(s * self.max_pages_per_seq + slot)
+            self._starts[s] = max(self._starts[s], start)
+        if flat_idx:
+            self.block_table.view(-1).index_copy_(
+                0, torch.tensor(flat_idx, dtype=torch.long).to(self.device),
+                torch.full((len(flat_idx),), -1, dtype=torch.int32).to(self.device))
+        return len(flat_idx)
+
+    def check_released(self, name: str, lows) -> None:
+        """Host-side guard of the attention entry points, from the mirrors
+        alone and before any launch.  lows[s] is the smallest key position the
+        call attends in sequence s (None: it attends nothing there), or
+        `lows` itself is None when the call has no window.  Raises ValueError
+        if a sequence with released pages would be read below host_starts."""
+        for s, start in enumerate(self._starts):
+            if start == 0:
+                continue
+            if lows is None:
+                raise ValueError(
+                    f"{name}: sequence {s} has released its first {start} keys "
+                    f"(release_prefix); pass the window they were released for")
+            if lows[s] is not None and lows[s] < start:
+                raise ValueError(
+                    f"{name}: sequence {s} would attend from key {lows[s]}, but "
+                    f"keys below {start} are released (release_prefix)")
+
     def free(self, seq: int) -> None:
-        """Return sequence `seq`'s pages to the pool and zero its length."""
-        self._free.extend(reversed(self._pages[seq]))
+        """Return the pages sequence `seq` still holds to the pool and zero
+        its length and its released prefix."""
+        self._free.extend(pg for pg in reversed(self._pages[seq]) if pg >= 0)
         self._pages[seq] = []
         self._lens[seq] = 0
+        self._starts[seq] = 0
         self.block_table[seq].fill_(-1)
         self.seq_lens[seq].fill_(0)
 
     # ---- read-back (debugging / tests) ----------------------------------
     def gather(self, seq: int) -> tuple[Tensor, Tensor]:
         """Dense (k, v), each (hk, seq_len, dim_head), of one sequence:
-        bf16 as stored, or fp32 dequantised for an fp8 cache."""
+        bf16 as stored, or fp32 dequantised for an fp8 cache.  Rows below
+        host_starts[seq] (released pages) come back as zeros, so positions
+        stay absolute."""
         n = self._lens[seq]
-        pages = torch.tensor(self._pages[seq], dtype=torch.long).to(self.device)
+        gone = self._starts[seq] // self.page_size
+        pages = torch.tensor([max(pg, 0) for pg in self._pages[seq]],
+                             dtype=torch.long).to(self.device)
 
         def dense(pool, scales):
             x = pool[pages]                                   # (np, hk, ps, D)
             if self.fp8:
                 x = (x.view(torch.float8_e4m3fn).float()
                      * torch.exp2(scales[pages].float() - 127.0).unsqueeze(-1))
+            if gone:
+                x[:gone] = 0
             x = x.permute(1, 0, 2, 3).reshape(self.kv_heads, -1, self.kernel_dim)
             return x[:, :n, :self.dim_head].contiguous()
 

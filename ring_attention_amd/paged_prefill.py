@@ -12,7 +12,9 @@ then attend, the convention of `tree_attn_decode_paged(causal=True)`.  Query
 t < q_lens[i] of sequence i sits at position seq_len[i] - q_lens[i] + t and
 attends keys [0, seq_len[i]); with `causal` only j <= position, with
 `window=w` only position - j <= w (the project's token-exact lookback, with
-or without `causal`).
+or without `causal`).  A cache whose pages below the window were released
+(`PagedKVCache.release_prefix`) is served only with a window that stays at
+or beyond the released prefix; anything else raises ValueError up front.
 """
 
 from __future__ import annotations
@@ -140,6 +142,14 @@ def paged_prefill_attn(
     if not 0 <= kv_split <= _MAX_SPLIT:
         raise ValueError(f"paged_prefill_attn: kv_split must lie in [0, {_MAX_SPLIT}]")
     lens = _host_q_lens(q_lens, b, t, cache.host_lens)
+    if any(cache.host_starts):
+        # released pages (PagedKVCache.release_prefix): the first live row of
+        # sequence i sits at seq_len - q_len and starts `window` keys back
+        cache.check_released(
+            "paged_prefill_attn",
+            None if window is None else
+            [max(0, n - ql - int(window)) if ql > 0 else None
+             for n, ql in zip(cache.host_lens, lens)])
 
     if not (q.is_cuda and use_hip_kernel is not False):
         out, lse = _eager(q, cache, lens, causal, window)

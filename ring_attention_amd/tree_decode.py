@@ -150,22 +150,65 @@ def tree_attn_decode_fp8(
     return _merge_across_ranks(local_out, lse, dtype, eps)
 
 
+def _window_spans(lens: list[int], after: list[int], nq: int, causal: bool,
+                 window: int) -> list[list[tuple[int, int]]]:
+    """Per sequence, the [lo, limit) key span of every query row (the
+    definition shared with paged_prefill_attn, in local key coordinates)."""
+    spans = []
+    for n, a in zip(lens, after):
+        rows = []
+        for iq in range(nq):
+            limit = max(0, n - (nq - 1 - iq)) if causal else n
+            rows.append((min(max(n + a - nq + iq - window, 0), limit), limit))
+        spans.append(rows)
+    return spans
+
+
 def _local_paged_decode_partial(q: Tensor, cache, causal: bool = False,
                                 use_hip_kernel: bool | None = None,
-                                chunks: int = 0) -> tuple[Tensor, Tensor]:
+                                chunks: int = 0, window: int | None = None,
+                                kv_after=None) -> tuple[Tensor, Tensor]:
     """Local flash-decode partial over a PagedKVCache:
     (out fp32 (b,h,nq,d), lse fp32 (b,h,nq,1)).
 
     q (b, h, nq, d) with b == cache.max_seqs and d == cache.dim_head (the
-    paged path requires dv == d).  Row (b, iq) attends keys [0, limit) of
+    paged path requires dv == d).  Row (b, iq) attends keys [lo, limit) of
     sequence b, limit = seq_lens[b], or with `causal`
     max(0, seq_lens[b] - (nq - 1 - iq)): the last nq cached positions are
-    the queries' own tokens.  A row whose limit is 0 returns out == 0 with a
-    finite lse <= -1e30, so it drops out of any later merge.
+    the queries' own tokens.  lo is 0 without a window; with `window=w` the
+    query sits at position seq_lens[b] + kv_after[b] - nq + iq in local key
+    coordinates (kv_after: tokens of the sequence held by LATER ranks, a host
+    list or int tensor read on the host, default 0) and
+    lo = clamp(position - w, 0, limit) — paged_prefill_attn's token-exact
+    lookback, with or without `causal`.  A row with lo == limit returns
+    out == 0 with a finite lse <= -1e30, so it drops out of any later merge.
+
+    A cache that has released pages (`release_prefix`) is only served with a
+    window whose rows all start at or beyond `cache.host_starts`; anything
+    else raises ValueError before a kernel is launched.
     """
     b, h, nq, d = q.shape
     assert b == cache.max_seqs and d == cache.dim_head
     assert h % cache.kv_heads == 0
+    if window is not None and window < 0:
+        raise ValueError("tree_attn_decode_paged: window must be >= 0")
+    after = None
+    if kv_after is not None:
+        after = [int(x) for x in (kv_after.tolist() if isinstance(kv_after, Tensor)
+                                  else kv_after)]
+        if len(after) != b or any(x < 0 for x in after):
+            raise ValueError(f"tree_attn_decode_paged: kv_after needs {b} "
+                             f"entries >= 0")
+    spans = None
+    if window is not None and (any(cache.host_starts) or not
+                               (q.is_cuda and use_hip_kernel is not False)):
+        spans = _window_spans(cache.host_lens, after or [0] * b, nq, causal,
+                             int(window))
+    if any(cache.host_starts):
+        cache.check_released(
+            "tree_attn_decode_paged",
+            None if spans is None else
+            [min((lo for lo, hi in rows if lo < hi), default=None) for rows in spans])
     if q.is_cuda and use_hip_kernel is not False:
         from .ops import hip_ext
         ext = hip_ext.require()       # no eager fallback on GPU
@@ -176,13 +219,17 @@ def _local_paged_decode_partial(q: Tensor, cache, causal: bool = False,
             qb.to(torch.bfloat16).contiguous(),
             cache.k_pages, cache.v_pages, cache.k_scales, cache.v_scales,
             cache.block_table, cache.seq_lens, cache.max_seq_len,
-            d ** -0.5, causal, chunks)
+            d ** -0.5, causal, chunks, window is not None,
+            0 if window is None else int(window),
+            None if window is None or after is None else
+            torch.tensor(after, dtype=torch.int32).to(q.device))
         out, lse = ext.decode_merge(outs, lses)
         if d != kd:
             out = out[..., :d]
         return out, lse
 
-    # eager fallback (CPU): gather each sequence, mask by length and tail
+    # eager fallback (CPU): gather each sequence, mask by length, tail and
+    # window (released rows gather as zeros and are always masked)
     scale = d ** -0.5
     hk = cache.kv_heads
     groups = h // hk
@@ -202,6 +249,10 @@ def _local_paged_decode_partial(q: Tensor, cache, causal: bool = False,
             limit = n - (nq - 1 - torch.arange(nq, device=q.device))
             masked = torch.arange(n, device=q.device)[None, :] >= limit[:, None]
             sim = sim.masked_fill(masked[None], float("-inf"))
+        if spans is not None:
+            lo = torch.tensor([r[0] for r in spans[i]], device=q.device)
+            masked = torch.arange(n, device=q.device)[None, :] < lo[:, None]
+            sim = sim.masked_fill(masked[None], float("-inf"))
         row_lse = sim.logsumexp(dim=-1, keepdim=True)   # -inf where limit <= 0
         live = torch.isfinite(row_lse)
         attn = torch.softmax(sim, dim=-1)
@@ -218,6 +269,8 @@ def tree_attn_decode_paged(
     causal: bool = False,
     eps: float = 1e-8,
     use_hip_kernel: bool | None = None,
+    window: int | None = None,
+    kv_after=None,
 ) -> Tensor:
     """Tree-attention decode over a paged KV cache with per-sequence lengths.
 
@@ -228,6 +281,17 @@ def tree_attn_decode_paged(
     `causal=True` only on the rank that holds the tail of the sequences: its
     last nq cached positions are then the queries' own tokens and query iq
     attends up to and including its own.
+
+    `window=w` is the token-exact lookback of RingAttention and
+    paged_prefill_attn: a query attends only the keys at most w positions
+    behind it.  The queries are the last nq tokens of each sequence, so a
+    rank that does not hold the tail passes `kv_after` (host list or int
+    tensor, one entry per sequence): the tokens of the sequence held by LATER
+    ranks.  A rank whose whole shard lies outside the window merges with
+    weight 0.  A cache that has released pages (`PagedKVCache.release_prefix`)
+    must be served with a window that stays at or beyond its released prefix;
+    otherwise ValueError is raised before anything runs.
     """
-    local_out, lse = _local_paged_decode_partial(q, cache, causal, use_hip_kernel)
+    local_out, lse = _local_paged_decode_partial(q, cache, causal, use_hip_kernel,
+                                                 window=window, kv_after=kv_after)
     return _merge_across_ranks(local_out, lse, q.dtype, eps)

@@ -13,7 +13,15 @@ Dense and paged measurements ALTERNATE inside every round (the box is shared)
 and the median over the rounds is reported; each measurement is `--iters`
 steps between two device events after a warm-up.
 
+`--window W [W ...]` adds the sliding-window groups: one sequence with
+`--kv-len` keys cached, decoded with `window=W`, against an UNWINDOWED step
+over a cache that holds exactly W + 1 keys (the same keys: the windowed row
+attends W + 1 of them), bf16 and fp8, every page size, alternating in the same
+rounds.  `vs_short` is windowed / short.  `--only-window` skips the dense
+groups.
+
     python tools/paged_decode_bench.py [--kv-len 131072] [--rounds 7] [--out F]
+        [--window 1024 4096 32768] [--only-window]
 """
 
 from __future__ import annotations
@@ -75,18 +83,20 @@ def ordered(fn, order):
     return step
 
 
-def run_group(name, steps, args, results, note=""):
-    """steps: {label: fn}; alternates all of them for `rounds` rounds."""
+def run_group(name, steps, args, results, note="", base_of=None, ratio="vs_dense"):
+    """steps: {label: fn}; alternates all of them for `rounds` rounds.
+    `base_of(label)` names the step a label is compared with (default
+    "dense"); the ratio of the medians is recorded under `ratio`."""
     samples = {label: [] for label in steps}
     for _ in range(args.rounds):
         for label, fn in steps.items():
             samples[label].append(time_us(fn, args.iters, args.warmup))
-    base = statistics.median(samples["dense"])
     for label, xs in samples.items():
         med = statistics.median(xs)
+        base = statistics.median(samples[base_of(label) if base_of else "dense"])
         rec = {"group": name, "config": label, "median_us": round(med, 2),
                "min_us": round(min(xs), 2), "max_us": round(max(xs), 2),
-               "vs_dense": round(med / base, 3), "rounds": len(xs), "note": note}
+               ratio: round(med / base, 3), "rounds": len(xs), "note": note}
         results.append(rec)
         print(json.dumps(rec), flush=True)
 
@@ -101,6 +111,11 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--page-sizes", type=int, nargs="+", default=[16, 64, 256])
+    ap.add_argument("--window", type=int, nargs="*", default=[],
+                    help="also time a windowed step over --kv-len cached keys "
+                         "against an unwindowed step over window + 1 keys")
+    ap.add_argument("--only-window", action="store_true",
+                    help="skip the dense-vs-paged groups")
     ap.add_argument("--out", default=None, help="also write the records here (JSON)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "paged_decode_bench needs a GPU"
@@ -136,12 +151,38 @@ def main():
     q = torch.randn(1, h, 1, d, device=dev, dtype=bf)
     k = torch.randn(1, hk, n, d, device=dev, dtype=bf)
     v = torch.randn(1, hk, n, d, device=dev, dtype=bf)
-    for fp8 in (False, True):
+
+    # ---- sliding window: kv-len cached, window w, vs w + 1 keys cached -----
+    for w in args.window:
+        assert 0 <= w < n
+        for fp8 in (False, True):
+            steps = {}
+            for ps in args.page_sizes:
+                full = PagedKVCache.from_dense(k, v, [n], ps, fp8=fp8, shuffle_seed=7)
+                short = PagedKVCache.from_dense(
+                    k[:, :, n - w - 1:].contiguous(), v[:, :, n - w - 1:].contiguous(),
+                    [w + 1], ps, fp8=fp8, shuffle_seed=7)
+                steps[f"short ps={ps}"] = (
+                    lambda c=short: _local_paged_decode_partial(q, c))
+                steps[f"window ps={ps}"] = (
+                    lambda c=full: _local_paged_decode_partial(q, c, window=w))
+                err = (steps[f"window ps={ps}"]()[0]
+                       - steps[f"short ps={ps}"]()[0]).abs().max().item()
+                assert err < 5e-3, (w, ps, err)
+            run_group(f"{'fp8' if fp8 else 'bf16'} b=1 kv={n} window={w}", steps, args,
+                      results, base_of=lambda label: label.replace("window", "short"),
+                      ratio="vs_short",
+                      note=f"short = unwindowed step over a cache of {w + 1} keys")
+            del steps
+    for fp8 in (False, True) if not args.only_window else ():
         steps = {"dense": dense_step(q, k, v, fp8)}
         steps.update(paged_steps(q, k, v, [n], fp8, ("identity", "shuffled"), "chunk"))
         check(steps)
         run_group(f"{'fp8' if fp8 else 'bf16'} b=1 kv={n}", steps, args, results)
         del steps
+
+    if args.only_window:
+        return write(args, results)
 
     # ---- uniform batch: b = 8 at kv / 4 (same bytes as dense, no padding) -
     b, nb = 8, n // 4
@@ -167,6 +208,10 @@ def main():
               note=f"dense is PADDED to {n} per sequence; the ragged batch "
                    f"holds {frac:.3f} of those bytes")
 
+    write(args, results)
+
+
+def write(args, results):
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
