@@ -63,13 +63,50 @@ struct FwdLds {
 // ---------------------------------------------------------------------------
 // forward kernel
 // ---------------------------------------------------------------------------
-template <int D, bool SOFTCLAMP, bool PAIRED>
+// How the per-q-tile body (attn_fwd_body.inc) is placed in the kernel.
+enum BodyForm {
+    BODY_DIRECT,   // at pit-loop scope, P aliases the kernel parameter
+    BODY_LAMBDA,   // directly-called lambda with a VALUE copy of the params
+    BODY_FRAME,    // the same lambda behind a noinline frame
+};
+
+// The form each instantiation keeps, chosen by measurement (fwd-only, same
+// box, TF; profiles/README.md "Lean forward instantiations").
+// Full-featured bodies keep what they had: PAIRED the frame (it confines
+// register allocation to the body, the pair loop's liveness otherwise spills
+// 532 B/lane); d128 plain the value copy (it frees the allocator from
+// aliasing p through the kernarg segment, 498 vs 424); d64 / d32 plain direct
+// (the lambda cost 264 B/lane of scratch and -3.5%, the frame -12%).
+// Lean bodies are direct everywhere.  The frame and the value copy were
+// remedies for register pressure the lean body does not have, and the frame
+// now only costs (direct / lambda / frame): d64 plain 554 / 536 / 473, d128
+// plain 699 / 683 / 570, d64 PAIRED 476 / 468 / 410, d128 PAIRED 607 / 611 /
+// 505, d32 PAIRED 281 / 283 / 205, d32 plain 326 / 329 / 227.  Direct and
+// lambda are within a run's spread at d128 PAIRED and d32; direct is the
+// simpler form and the only one with no scratch in the plain kernels.
+// To measure the forms again, build with -DFWD_LEAN_FORM=0|1|2 (BodyForm
+// value): every lean instantiation then takes that form.  The figures above
+// came from a build that chose the form per launch instead; the kernels are
+// the same.
+#ifndef FWD_LEAN_FORM
+#define FWD_LEAN_FORM BODY_DIRECT
+#endif
+constexpr BodyForm fwd_body_form(int d, bool paired, bool lean) {
+    if (lean) return (BodyForm)FWD_LEAN_FORM;
+    return paired ? BODY_FRAME : d == 128 ? BODY_LAMBDA : BODY_DIRECT;
+}
+
+// LEAN: the body without ticks, ablate, key-pad mask and bias (see the
+// header of attn_fwd_body.inc); launch_attn_fwd picks it when none is set.
+template <int D, bool SOFTCLAMP, bool PAIRED, bool LEAN>
 __global__ __launch_bounds__(NTHREADS, 1) void attn_fwd_kernel(FwdParams p) {
     static_assert(D % 32 == 0);
     constexpr int DBLK = D / 32;     // 32-d output blocks
     constexpr int KSTEPS = D / 16;   // QK^T k-steps
     constexpr int KVBLK = kvblk(D);
     constexpr int NBLK = KVBLK / 32;
+
+    constexpr BodyForm FORM = fwd_body_form(D, PAIRED, LEAN);
 
     __shared__ FwdLds<D> lds;
 
@@ -96,7 +133,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void attn_fwd_kernel(FwdParams p) {
         __syncthreads();                       // LDS handoff between tiles
     }
 
-    if constexpr (PAIRED) {
+    if constexpr (FORM == BODY_FRAME) {
         auto fwd_body = [&]() {
             const FwdParams P = p;   // register-local copy: the noinline
                                      // frame would otherwise re-read
@@ -106,11 +143,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void attn_fwd_kernel(FwdParams p) {
             #undef FWD_EXIT
         };
         noinline_call(fwd_body);
-    } else if constexpr (D == 128) {
-        // d128-plain prefers the directly-called lambda with a VALUE copy of
-        // the params (measured fwd-only 498 vs 424 TF): the copy frees the
-        // allocator from aliasing p through the kernarg segment, and the
-        // extra scratch sits outside the hot loop
+    } else if constexpr (FORM == BODY_LAMBDA) {
         auto fwd_body = [&]() {
             const FwdParams P = p;
             #define FWD_EXIT return
@@ -206,6 +239,17 @@ void launch_attn_fwd_merge(const FwdMergeParams& p, int head_dim, hipStream_t st
     }
 }
 
+template <int D, bool LEAN>
+static void launch_fwd_d(const FwdParams& p, dim3 grid, dim3 block, hipStream_t stream) {
+    if (p.softclamp) {
+        if (p.paired > 0) hipLaunchKernelGGL((attn_fwd_kernel<D, true, true, LEAN>), grid, block, 0, stream, p);
+        else hipLaunchKernelGGL((attn_fwd_kernel<D, true, false, LEAN>), grid, block, 0, stream, p);
+    } else {
+        if (p.paired > 0) hipLaunchKernelGGL((attn_fwd_kernel<D, false, true, LEAN>), grid, block, 0, stream, p);
+        else hipLaunchKernelGGL((attn_fwd_kernel<D, false, false, LEAN>), grid, block, 0, stream, p);
+    }
+}
+
 void launch_attn_fwd(const FwdParams& p, int head_dim, hipStream_t stream) {
     // v2 (one-wave-per-SIMD pipeline) opt-in via RING_ATTN_FWD_V2=1;
     // RING_ATTN_FWD_V2=0 forces v1.  Default currently v1 (flip after the
@@ -218,22 +262,17 @@ void launch_attn_fwd(const FwdParams& p, int head_dim, hipStream_t stream) {
     dim3 grid(p.paired ? (qtiles + 1) / 2 : qtiles, p.b * p.h,
               p.kv_split > 1 ? p.kv_split : 1);
     dim3 block(NTHREADS);
-    const bool pr = p.paired > 0;
+    // lean exactly when none of the four cold features is asked for
+    const bool lean = !p.kmask && !p.bias && !p.ticks && p.ablate == 0;
     if (head_dim == 64) {
-        if (p.softclamp) if (pr) hipLaunchKernelGGL((attn_fwd_kernel<64, true, true>), grid, block, 0, stream, p);
-        else hipLaunchKernelGGL((attn_fwd_kernel<64, true, false>), grid, block, 0, stream, p);
-        else if (pr) hipLaunchKernelGGL((attn_fwd_kernel<64, false, true>), grid, block, 0, stream, p);
-        else hipLaunchKernelGGL((attn_fwd_kernel<64, false, false>), grid, block, 0, stream, p);
+        if (lean) launch_fwd_d<64, true>(p, grid, block, stream);
+        else launch_fwd_d<64, false>(p, grid, block, stream);
     } else if (head_dim == 128) {
-        if (p.softclamp) if (pr) hipLaunchKernelGGL((attn_fwd_kernel<128, true, true>), grid, block, 0, stream, p);
-        else hipLaunchKernelGGL((attn_fwd_kernel<128, true, false>), grid, block, 0, stream, p);
-        else if (pr) hipLaunchKernelGGL((attn_fwd_kernel<128, false, true>), grid, block, 0, stream, p);
-        else hipLaunchKernelGGL((attn_fwd_kernel<128, false, false>), grid, block, 0, stream, p);
+        if (lean) launch_fwd_d<128, true>(p, grid, block, stream);
+        else launch_fwd_d<128, false>(p, grid, block, stream);
     } else if (head_dim == 32) {
-        if (p.softclamp) if (pr) hipLaunchKernelGGL((attn_fwd_kernel<32, true, true>), grid, block, 0, stream, p);
-        else hipLaunchKernelGGL((attn_fwd_kernel<32, true, false>), grid, block, 0, stream, p);
-        else if (pr) hipLaunchKernelGGL((attn_fwd_kernel<32, false, true>), grid, block, 0, stream, p);
-        else hipLaunchKernelGGL((attn_fwd_kernel<32, false, false>), grid, block, 0, stream, p);
+        if (lean) launch_fwd_d<32, true>(p, grid, block, stream);
+        else launch_fwd_d<32, false>(p, grid, block, stream);
     } else {
         // unsupported head dim is a host-side error (checked in bindings)
         __builtin_trap();

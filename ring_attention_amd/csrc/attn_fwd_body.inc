@@ -1,14 +1,33 @@
-// forward-kernel per-q-tile body — textually included TWICE by
-// attn_fwd.hip (preprocessor include, not a header):
-//   * PAIRED instantiations: inside a lambda passed to noinline_call —
-//     the noinline frame confines register allocation to the body (the pair
-//     loop's liveness otherwise spills 532 B/lane; measured +5% causal)
-//   * plain instantiations: directly at pit-loop scope — the SAME body via
-//     an inlined lambda costs 264 B/lane of scratch and -3.5% fwd-only
-//     (measured 454 vs 471 TF same box), and via the noinline frame -12%,
-//     so plain keeps the original form
+// forward-kernel per-q-tile body — textually included THREE times by
+// attn_fwd.hip (preprocessor include, not a header), once per BodyForm; which
+// instantiation takes which form, and the measurements, are at
+// fwd_body_form() there:
+//   * BODY_FRAME, inside a lambda passed to noinline_call (full-featured
+//     PAIRED): the noinline frame confines register allocation to the body
+//     (the pair loop's liveness otherwise spills 532 B/lane; measured +5%
+//     causal)
+//   * BODY_LAMBDA, a directly-called lambda with a value copy of the params
+//     (full-featured d128 plain)
+//   * BODY_DIRECT, at pit-loop scope (every LEAN instantiation; full-featured
+//     d64 / d32 plain, where the SAME body via an inlined lambda costs
+//     264 B/lane of scratch and -3.5% fwd-only, 454 vs 471 TF same box, and
+//     via the noinline frame -12%)
 // Context expected at inclusion: P (FwdParams value or reference), qtile,
-// lds, tid/lane/wid/l31/lhi, b/h/hk, and FWD_EXIT (return | continue).
+// lds, tid/lane/wid/l31/lhi, b/h/hk, LEAN, and FWD_EXIT (return | continue).
+//
+// LEAN (constexpr bool) compiles the body WITHOUT the four cold features:
+// the ticks stamps, the ablate switches, the key-pad mask and the bias.  They
+// are `if constexpr (!LEAN)`, not folded run-time tests: as run-time branches
+// in the tile loop they cost the d64 plain kernel 64 v_mov_b64 per tile (phi
+// copies of s[] and o_acc forced by the ablate == 2 exit and the block cuts
+// of the stamp branches), spills in the loop, and at d128 556 B/lane of
+// scratch.  The lean body also loads full tiles without per-lane predicates
+// and keeps the O rescale single-issue.  !LEAN is the code as it was,
+// instruction for instruction; the launcher picks LEAN exactly when none of
+// the four features is asked for.  The arithmetic of the two is the same.
+#define FWD_STAMP(n)                                                          \
+    if constexpr (!LEAN)                                                      \
+        if (stamp) P.ticks[t * 6 + (n)] = __builtin_amdgcn_s_memtime()
     const long irow0 = (long)qtile * QROWS_WG + wid * QROWS_WAVE;  // this wave's first q row
     const long i = irow0 + l31;                                     // this lane's q row
     const bool row_valid = i < P.nq;
@@ -68,7 +87,9 @@
     constexpr int VREGS = (VPAIRS + NTHREADS - 1) / NTHREADS;
     const __bf16* kbase = (const __bf16*)P.k + ((long)b * P.nk) * P.hk * D + (long)hk * D;
     const __bf16* vbase = (const __bf16*)P.v + ((long)b * P.nk) * P.hk * D + (long)hk * D;
-    const unsigned char* mbase = P.kmask ? (const unsigned char*)P.kmask + (long)b * P.nk : nullptr;
+    const unsigned char* mbase = nullptr;
+    if constexpr (!LEAN)
+        mbase = P.kmask ? (const unsigned char*)P.kmask + (long)b * P.nk : nullptr;
 
     uint4 kst[KREGS];
     bf16x8 vsta[VREGS], vstb[VREGS];
@@ -85,34 +106,65 @@
         + ((tid % (KVBLK / 2)) * 2) * kv_row_stride + (tid / (KVBLK / 2)) * 8;
     const __bf16* vptrb = vptra + kv_row_stride;
     long j0_next = (long)t_lo * KVBLK;
+    long j0_staged = j0_next;   // LEAN: first key of the tile in the staging registers
 
     auto load_tile = [&]() {
         const long j0 = j0_next;
         const long jmax = min(j0 + KVBLK, P.nk) - 1;
         const bool full = jmax - j0 == KVBLK - 1;
-        #pragma unroll
-        for (int r = 0; r < KREGS; ++r) {
-            int c = tid + r * NTHREADS;
-            if (c < KCHUNKS) {
-                const __bf16* src = kptr + (long)(r * (NTHREADS / CH_PER_ROW)) * kv_row_stride;
-                kst[r] = (full || (j0 + c / CH_PER_ROW) <= jmax)
-                         ? *(const uint4*)src : uint4{0, 0, 0, 0};
+        if constexpr (LEAN) {
+            // Every load is unconditional: a row past the end of the ragged
+            // last tile reads key row 0 instead and is zeroed when the tile
+            // goes to LDS (write_tile, one scalar branch).  A
+            // `valid ? load : 0` here is a 64-bit v_cmp, a saveexec, a
+            // branch and a zero fill around each load, on every tile.
+            constexpr int KROW_STEP = NTHREADS / CH_PER_ROW;
+            constexpr int VD_STEP = (NTHREADS / (KVBLK / 2)) * 8;
+            #pragma unroll
+            for (int r = 0; r < KREGS; ++r) {
+                int c = tid + r * NTHREADS;
+                if (c < KCHUNKS) {
+                    const bool ok = full || (j0 + c / CH_PER_ROW) <= jmax;
+                    kst[r] = *(const uint4*)(ok ? kptr + (long)(r * KROW_STEP) * kv_row_stride
+                                                : kbase + (tid % CH_PER_ROW) * 8);
+                }
             }
-        }
-        #pragma unroll
-        for (int r = 0; r < VREGS; ++r) {
-            int c = tid + r * NTHREADS;
-            if (c < VPAIRS) {
-                // extra r steps advance along d (same kv pair)
-                const __bf16* sa = vptra + r * (NTHREADS / (KVBLK / 2)) * 8;
-                const __bf16* sb = vptrb + r * (NTHREADS / (KVBLK / 2)) * 8;
-                long ja = j0 + (c % (KVBLK / 2)) * 2;
-                vsta[r] = (full || ja <= jmax) ? *(const bf16x8*)sa : bf16x8{};
-                vstb[r] = (full || ja + 1 <= jmax) ? *(const bf16x8*)sb : bf16x8{};
+            #pragma unroll
+            for (int r = 0; r < VREGS; ++r) {
+                int c = tid + r * NTHREADS;
+                if (c < VPAIRS) {
+                    const long ja = j0 + (c % (KVBLK / 2)) * 2;
+                    const __bf16* row0 = vbase + (tid / (KVBLK / 2)) * 8 + r * VD_STEP;
+                    vsta[r] = *(const bf16x8*)((full || ja <= jmax) ? vptra + r * VD_STEP : row0);
+                    vstb[r] = *(const bf16x8*)((full || ja + 1 <= jmax) ? vptrb + r * VD_STEP : row0);
+                }
             }
+            j0_staged = j0;
+        } else {
+            #pragma unroll
+            for (int r = 0; r < KREGS; ++r) {
+                int c = tid + r * NTHREADS;
+                if (c < KCHUNKS) {
+                    const __bf16* src = kptr + (long)(r * (NTHREADS / CH_PER_ROW)) * kv_row_stride;
+                    kst[r] = (full || (j0 + c / CH_PER_ROW) <= jmax)
+                             ? *(const uint4*)src : uint4{0, 0, 0, 0};
+                }
+            }
+            #pragma unroll
+            for (int r = 0; r < VREGS; ++r) {
+                int c = tid + r * NTHREADS;
+                if (c < VPAIRS) {
+                    // extra r steps advance along d (same kv pair)
+                    const __bf16* sa = vptra + r * (NTHREADS / (KVBLK / 2)) * 8;
+                    const __bf16* sb = vptrb + r * (NTHREADS / (KVBLK / 2)) * 8;
+                    long ja = j0 + (c % (KVBLK / 2)) * 2;
+                    vsta[r] = (full || ja <= jmax) ? *(const bf16x8*)sa : bf16x8{};
+                    vstb[r] = (full || ja + 1 <= jmax) ? *(const bf16x8*)sb : bf16x8{};
+                }
+            }
+            if (mbase && tid < KVBLK)
+                mst = (j0 + tid <= jmax) ? mbase[j0 + tid] : 0;
         }
-        if (mbase && tid < KVBLK)
-            mst = (j0 + tid <= jmax) ? mbase[j0 + tid] : 0;
         kptr += tile_stride;
         vptra += tile_stride;
         vptrb += tile_stride;
@@ -120,6 +172,20 @@
     };
 
     auto write_tile = [&](int par) {
+        if constexpr (LEAN) {
+            const long rows = P.nk - j0_staged;      // valid rows of the staged tile
+            if (rows < KVBLK) {                      // ragged last tile: the rest are 0
+                #pragma unroll
+                for (int r = 0; r < KREGS; ++r)
+                    if ((tid + r * NTHREADS) / CH_PER_ROW >= rows) kst[r] = uint4{0, 0, 0, 0};
+                #pragma unroll
+                for (int r = 0; r < VREGS; ++r) {
+                    const int la = ((tid + r * NTHREADS) % (KVBLK / 2)) * 2;
+                    if (la >= rows) vsta[r] = bf16x8{};
+                    if (la + 1 >= rows) vstb[r] = bf16x8{};
+                }
+            }
+        }
         #pragma unroll
         for (int r = 0; r < KREGS; ++r) {
             int c = tid + r * NTHREADS;
@@ -145,7 +211,8 @@
                 }
             }
         }
-        if (mbase && tid < KVBLK) lds.kmask[par][tid] = mst;
+        if constexpr (!LEAN)
+            if (mbase && tid < KVBLK) lds.kmask[par][tid] = mst;
     };
 
     // 3-deep pipeline over DOUBLE-buffered LDS: one barrier per tile; LDS
@@ -154,23 +221,29 @@
     if (t_lo < t_hi) {
         load_tile();
         write_tile(t_lo & 1);
-        if (P.ablate == 1) write_tile((t_lo & 1) ^ 1);   // both buffers valid
-        if (t_lo + 1 < t_hi && P.ablate != 1) load_tile();
+        if constexpr (LEAN) {
+            if (t_lo + 1 < t_hi) load_tile();
+        } else {
+            if (P.ablate == 1) write_tile((t_lo & 1) ^ 1);   // both buffers valid
+            if (t_lo + 1 < t_hi && P.ablate != 1) load_tile();
+        }
     }
 
     for (int t = t_lo; t < t_hi; ++t) {
         const int par = t & 1;
         const long j0 = (long)t * KVBLK;
         const long jmax = min(j0 + KVBLK, P.nk) - 1;
-        const bool full_tile =
+        bool full_tile =
             (jmax - j0 == KVBLK - 1) &&
-            M.uncut(wg_q_min, wg_q_max, j0, jmax) &&
-            !P.kmask && !P.bias;
+            M.uncut(wg_q_min, wg_q_max, j0, jmax);
+        if constexpr (!LEAN) full_tile = full_tile && !P.kmask && !P.bias;
 
         __syncthreads();
-        const bool stamp = P.ticks && blockIdx.x == 0 && bh == 0 && tid == 0
-                           && blockIdx.z == 0;
-        if (stamp) P.ticks[t * 6 + 0] = __builtin_amdgcn_s_memtime();
+        bool stamp = false;
+        if constexpr (!LEAN)
+            stamp = P.ticks && blockIdx.x == 0 && bh == 0 && tid == 0
+                    && blockIdx.z == 0;
+        FWD_STAMP(0);
 
         // ---- QK^T: S^T[kv][q] for the NBLK 32-row kv blocks
         f32x16 s[NBLK];
@@ -188,16 +261,18 @@
             }
         }
         __builtin_amdgcn_s_setprio(0);
-        if (stamp) P.ticks[t * 6 + 1] = __builtin_amdgcn_s_memtime();
+        FWD_STAMP(1);
 
         // stage tile t+1 into the other buffer while the MFMAs above retire
-        if (P.ablate != 1) {
+        bool restage = true;
+        if constexpr (!LEAN) restage = P.ablate != 1;
+        if (restage) {
             if (t + 1 < t_hi) write_tile(par ^ 1);
             if (t + 2 < t_hi) load_tile();
         }
-        if (stamp) P.ticks[t * 6 + 2] = __builtin_amdgcn_s_memtime();
+        FWD_STAMP(2);
 
-        if (P.ablate == 2) {
+        if constexpr (!LEAN) if (P.ablate == 2) {
             // diagnostics: skip softmax VALU, feed PV garbage fragments kept
             // alive via asm (rule 17: a skipped phase must not DCE upstream)
             uint32_t gfrag[4];
@@ -262,7 +337,7 @@
                     }
                     long j = j0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
                     bool ok = j <= jmax;
-                    if (P.bias && ok) {
+                    if constexpr (!LEAN) if (P.bias && ok) {
                         // reference semantics: sim = qk*scale + bias
                         // (natural log), applied after softclamp; our
                         // softmax runs in the exp2 domain
@@ -272,14 +347,15 @@
                         x += P.bias[bi] * LOG2E;
                     }
                     ok = M.attends(qpos_i, j, ok);
-                    if (P.kmask) ok = ok && lds.kmask[par][j - j0];
+                    if constexpr (!LEAN)
+                        if (P.kmask) ok = ok && lds.kmask[par][j - j0];
                     if (!ok) x = MASK_VALUE_F;
                     s[kb][r] = x;
                     smax = fmaxf(smax, x);
                 }
         }
         smax = fmaxf(smax, cross_half(smax));
-        if (stamp) P.ticks[t * 6 + 3] = __builtin_amdgcn_s_memtime();
+        FWD_STAMP(3);
 
         // ---- online softmax update (defer-max THR=0: exact — skip the O
         // rescale whenever the running max did not grow on any lane)
@@ -313,10 +389,16 @@
         if (any_growth) {
             float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
             l_run = l_run * alpha + rowsum;
+            // LEAN: single-issue multiplies (mul_f32) — written plainly the
+            // block is SLP-packed into v_pk_mul_f32, a loss beside MFMAs;
+            // same IEEE product per element
             #pragma unroll
             for (int db = 0; db < DBLK; ++db)
                 #pragma unroll
-                for (int r = 0; r < 16; ++r) o_acc[db][r] *= alpha;
+                for (int r = 0; r < 16; ++r) {
+                    if constexpr (LEAN) o_acc[db][r] = mul_f32(o_acc[db][r], alpha);
+                    else o_acc[db][r] *= alpha;
+                }
             m_run = m_new;
         } else {
             l_run += rowsum;
@@ -329,7 +411,7 @@
         // The vt image is staged in this k order (kperm_pair), so
         // pk[4*ks .. 4*ks+3] IS the fragment of k-step ks — no lane exchange.
 
-        if (stamp) P.ticks[t * 6 + 4] = __builtin_amdgcn_s_memtime();
+        FWD_STAMP(4);
         // ---- PV: O^T[d][q] += V^T[d][kv] P^T[kv][q]
         __builtin_amdgcn_s_setprio(1);
         #pragma unroll
@@ -344,7 +426,7 @@
             }
         }
         __builtin_amdgcn_s_setprio(0);
-        if (stamp) P.ticks[t * 6 + 5] = __builtin_amdgcn_s_memtime();
+        FWD_STAMP(5);
     }
 
     // ---- epilogue
@@ -399,3 +481,5 @@
                 oa[(long)d * P.nq + i] = o_acc[db][r];
             }
     }
+
+#undef FWD_STAMP
