@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdint>
 
 #ifdef __HIPCC__
@@ -323,6 +324,15 @@ struct DecodeParams {
     const void* kscale;     // fp8 mode: e8m0 per kv row (B, HK, N)
     const void* vscale;     // fp8 mode: e8m0 per kv row (B, HK, N)
 };
+
+// Default kv-split S of every decode partial: ~512 keys per wave over the
+// longest key span a row covers, total waves capped near 8192, S capped at 256
+// (the chunk merge grows with S).  GPU-swept; the figures are at bindings.cpp's
+// decode_partials.
+inline long decode_default_chunks(long span, long waves) {
+    return std::max(1L, std::min(std::min(span / 512 + 1, 256L),
+                                 8192L / std::max(waves, 1L)));
+}
 
 void launch_decode_partial(const DecodeParams& p, int head_dim, hipStream_t stream);
 void launch_decode_partial_fp8(const DecodeParams& p, int head_dim, hipStream_t stream);

@@ -327,6 +327,32 @@ at::Tensor rotary_apply(at::Tensor x, at::Tensor cos_t, at::Tensor sin_t, double
     return out;
 }
 
+// What the three decode-partial bindings share: the kv-split S, the fp32
+// partials (out (S,B,H,NQ,D), lse (S,B,H,NQ,1)) and the default sm_scale.
+// S is chunks_in when forced, else decode_default_chunks on `span`, the
+// longest key span of a row (GPU-swept, tools/*decode_sweep*.py: 128k/1M
+// bf16: 155/983 -> 112/607 us; fp8: 109/250 -> 60/247 us; GQA 32q/4kv:
+// 229 -> 177 us).
+struct DecodePartials {
+    at::Tensor out, lse;
+    int64_t chunks;
+    float scale;
+};
+
+static DecodePartials decode_partials(const at::Tensor& q, int64_t span,
+                                      int64_t chunks_in, double sm_scale) {
+    const int64_t B = q.size(0), H = q.size(1), NQ = q.size(2), D = q.size(3);
+    const int64_t waves = B * H * NQ;
+    DecodePartials r;
+    r.chunks = chunks_in > 0 ? chunks_in : decode_default_chunks(span, waves);
+    TORCH_CHECK(r.chunks <= 65535, "chunks must fit grid.y");
+    TORCH_CHECK((waves + 3) / 4 * r.chunks < (int64_t(1) << 31), "grid too large");
+    r.out = at::empty({r.chunks, B, H, NQ, D}, q.options().dtype(at::kFloat));
+    r.lse = at::empty({r.chunks, B, H, NQ, 1}, q.options().dtype(at::kFloat));
+    r.scale = sm_scale > 0 ? (float)sm_scale : (float)(1.0 / std::sqrt((double)D));
+    return r;
+}
+
 std::vector<at::Tensor> decode_partial(at::Tensor q, at::Tensor k, at::Tensor v,
                                        double sm_scale, int64_t chunks_in) {
     // q (B,HQ,NQ,D); k,v (B,HK,N,D) bf16 — NQ query tokens (speculative /
@@ -338,25 +364,16 @@ std::vector<at::Tensor> decode_partial(at::Tensor q, at::Tensor k, at::Tensor v,
     const int64_t HK = k.size(1), N = k.size(2);
     TORCH_CHECK(D == 64 || D == 128, "head dim must be 64 or 128");
     TORCH_CHECK(H % HK == 0, "q heads must be a multiple of kv heads");
-    int64_t waves = B * H * NQ;
-    // kv-split heuristic (GPU-swept, tools/*decode_sweep*.py): ~512 keys
-    // per wave with total waves capped near 8192 and S capped at 256 (the
-    // host-side partial merge grows with S).  128k/1M bf16: 155/983 ->
-    // 112/607 us; fp8: 109/250 -> 60/247 us; GQA 32q/4kv: 229 -> 177 us.
-    int64_t chunks = chunks_in > 0 ? chunks_in : std::max<int64_t>(
-        1, std::min<int64_t>(std::min<int64_t>(N / 512 + 1, 256),
-                             8192 / std::max<int64_t>(waves, 1)));
-    auto out = at::empty({chunks, B, H, NQ, D}, q.options().dtype(at::kFloat));
-    auto lse = at::empty({chunks, B, H, NQ, 1}, q.options().dtype(at::kFloat));
+    DecodePartials r = decode_partials(q, N, chunks_in, sm_scale);
     DecodeParams p{};
     p.q = q.data_ptr(); p.k = k.data_ptr(); p.v = v.data_ptr();
-    p.out = out.data_ptr<float>(); p.lse = lse.data_ptr<float>();
+    p.out = r.out.data_ptr<float>(); p.lse = r.lse.data_ptr<float>();
     p.b = (int)B; p.h = (int)H; p.hk = (int)HK; p.nq = (int)NQ; p.n = N;
-    p.scale = sm_scale > 0 ? (float)sm_scale : (float)(1.0 / std::sqrt((double)D));
-    p.chunks = chunks;
+    p.scale = r.scale;
+    p.chunks = r.chunks;
     launch_decode_partial(p, (int)D, at::hip::getCurrentHIPStream());
     TORCH_CHECK(hipGetLastError() == hipSuccess, "decode launch failed");
-    return {out, lse};
+    return {r.out, r.lse};
 }
 
 std::vector<at::Tensor> attn_fwd_fp8(at::Tensor q8, at::Tensor k8, at::Tensor v8t,
@@ -420,26 +437,17 @@ std::vector<at::Tensor> decode_partial_fp8(at::Tensor q, at::Tensor k8, at::Tens
     TORCH_CHECK(D == 64 || D == 128, "head dim must be 64 or 128");
     TORCH_CHECK(H % HK == 0, "q heads must be a multiple of kv heads");
     TORCH_CHECK(ks.numel() == B * HK * N && vs.numel() == B * HK * N);
-    int64_t waves = B * H * NQ;
-    // kv-split heuristic (GPU-swept, tools/*decode_sweep*.py): ~512 keys
-    // per wave with total waves capped near 8192 and S capped at 256 (the
-    // host-side partial merge grows with S).  128k/1M bf16: 155/983 ->
-    // 112/607 us; fp8: 109/250 -> 60/247 us; GQA 32q/4kv: 229 -> 177 us.
-    int64_t chunks = chunks_in > 0 ? chunks_in : std::max<int64_t>(
-        1, std::min<int64_t>(std::min<int64_t>(N / 512 + 1, 256),
-                             8192 / std::max<int64_t>(waves, 1)));
-    auto out = at::empty({chunks, B, H, NQ, D}, q.options().dtype(at::kFloat));
-    auto lse = at::empty({chunks, B, H, NQ, 1}, q.options().dtype(at::kFloat));
+    DecodePartials r = decode_partials(q, N, chunks_in, sm_scale);
     DecodeParams p{};
     p.q = q.data_ptr(); p.k = k8.data_ptr(); p.v = v8.data_ptr();
     p.kscale = ks.data_ptr(); p.vscale = vs.data_ptr();
-    p.out = out.data_ptr<float>(); p.lse = lse.data_ptr<float>();
+    p.out = r.out.data_ptr<float>(); p.lse = r.lse.data_ptr<float>();
     p.b = (int)B; p.h = (int)H; p.hk = (int)HK; p.nq = (int)NQ; p.n = N;
-    p.scale = sm_scale > 0 ? (float)sm_scale : (float)(1.0 / std::sqrt((double)D));
-    p.chunks = chunks;
+    p.scale = r.scale;
+    p.chunks = r.chunks;
     launch_decode_partial_fp8(p, (int)D, at::hip::getCurrentHIPStream());
     TORCH_CHECK(hipGetLastError() == hipSuccess, "decode fp8 launch failed");
-    return {out, lse};
+    return {r.out, r.lse};
 }
 
 std::vector<at::Tensor> decode_merge(at::Tensor outs, at::Tensor lses) {
@@ -541,27 +549,19 @@ std::vector<at::Tensor> decode_partial_paged(
                     && kv_after->device() == q.device(),
                     "kv_after must be contiguous int32 (B,) on q's device");
     }
-    int64_t waves = B * H * NQ;
-    // the dense bindings' swept kv-split heuristic (~512 keys per wave,
-    // waves capped near 8192, S <= 256) on the longest sequence, or with a
-    // window on the longest row span (launch_decode_partial_paged)
+    // the kv-split follows the longest sequence, or with a window the
+    // longest row span (launch_decode_partial_paged)
     const int64_t span = has_win ? std::min<int64_t>(max_seq_len, win + NQ + 63)
                                  : max_seq_len;
-    int64_t chunks = chunks_in > 0 ? chunks_in : std::max<int64_t>(
-        1, std::min<int64_t>(std::min<int64_t>(span / 512 + 1, 256),
-                             8192 / std::max<int64_t>(waves, 1)));
-    TORCH_CHECK(chunks <= 65535, "chunks must fit grid.y");
-    TORCH_CHECK((waves + 3) / 4 * chunks < (int64_t(1) << 31), "grid too large");
-    auto out = at::empty({chunks, B, H, NQ, D}, q.options().dtype(at::kFloat));
-    auto lse = at::empty({chunks, B, H, NQ, 1}, q.options().dtype(at::kFloat));
-    if (waves == 0) return {out, lse};
+    DecodePartials r = decode_partials(q, span, chunks_in, sm_scale);
+    if (B * H * NQ == 0) return {r.out, r.lse};
     PagedDecodeParams p{};
     p.q = q.data_ptr();
     p.k_pages = k_pages.data_ptr(); p.v_pages = v_pages.data_ptr();
     if (fp8) { p.kscale = k_scales->data_ptr(); p.vscale = v_scales->data_ptr(); }
     p.block_table = block_table.data_ptr<int>();
     p.seq_lens = seq_lens.data_ptr<int>();
-    p.out = out.data_ptr<float>(); p.lse = lse.data_ptr<float>();
+    p.out = r.out.data_ptr<float>(); p.lse = r.lse.data_ptr<float>();
     p.b = (int)B; p.h = (int)H; p.hk = (int)HK; p.nq = (int)NQ;
     p.page_shift = shift;
     p.max_pages = (int)block_table.size(1);
@@ -575,15 +575,15 @@ std::vector<at::Tensor> decode_partial_paged(
     const char* order = std::getenv("RING_ATTN_PAGED_ORDER");
     p.chunk_major = order && order[0] == 'r' ? 0
                   : order && order[0] == 'c' ? 1 : (B > 1 ? 1 : 0);
-    p.scale = sm_scale > 0 ? (float)sm_scale : (float)(1.0 / std::sqrt((double)D));
-    p.chunks = chunks;
+    p.scale = r.scale;
+    p.chunks = r.chunks;
     p.max_seq_len = max_seq_len;
     p.has_win = has_win ? 1 : 0;
     p.win = has_win ? win : 0;
     p.kv_after = has_win && kv_after.has_value() ? kv_after->data_ptr<int>() : nullptr;
     launch_decode_partial_paged(p, (int)D, fp8, at::hip::getCurrentHIPStream());
     TORCH_CHECK(hipGetLastError() == hipSuccess, "paged decode launch failed");
-    return {out, lse};
+    return {r.out, r.lse};
 }
 
 void paged_kv_append(

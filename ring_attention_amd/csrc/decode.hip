@@ -9,13 +9,14 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
-#include "attn_common.h"
+#include "decode_common.h"
 
 namespace ring_attn {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-template <int D>
+// FP8 = the KV cache is 8-bit (half the HBM bytes — decode is bandwidth-
+// bound, measured 1.5-1.6 TB/s on the bf16 stream): k/v are e4m3 rows with
+// one e8m0 scale per kv row (kscale/vscale); q stays bf16.
+template <int D, bool FP8>
 __global__ __launch_bounds__(256) void decode_partial_kernel(DecodeParams p) {
     // one wave per (b, q-head, query token); 4 waves per block; blockIdx.y
     // splits the KV range into `chunks` partials (merged on the host) so
@@ -26,237 +27,54 @@ __global__ __launch_bounds__(256) void decode_partial_kernel(DecodeParams p) {
     const int rows = p.b * p.h * p.nq;
     const int wave_global = (blockIdx.x * 4) + (threadIdx.x >> 6);
     if (wave_global >= rows) return;
-    // group-major wave->row mapping: consecutive waves (the 4 of a block,
-    // which land on ONE CU and one XCD L2) cover the query tokens and then
-    // the GQA group-mates of the SAME kv head, so their shared kv stream is
-    // fetched once per L2.  The natural (b,h,iq) order instead put 4
-    // DIFFERENT kv heads in each block and scattered a group's readers
-    // across the 8 XCDs' private L2s — each re-fetched the stream from HBM
-    // (measured: 32q/4kv nq=1 decode at 0.27 TB/s effective).  Output
-    // layout is unchanged; only the wave->row assignment differs.
-    const int G = p.h / p.hk;
-    const int iq = wave_global % p.nq;
-    int r = wave_global / p.nq;
-    const int g = r % G;  r /= G;
-    const int hk = r % p.hk;           // reference tile GQA pairing
-    const int b = r / p.hk;
-    const int h = hk + g * p.hk;       // group-mate g of kv head hk
-    const int bh = b * p.h + h;
+    const DecodeRow r = decode_row(wave_global, p.h, p.hk, p.nq);
     const int lane = threadIdx.x & 63;
     const int chunk = blockIdx.y;
     const long per = (p.n + gridDim.y - 1) / gridDim.y;
     const long j_lo = chunk * per;
     const long j_hi = min(p.n, j_lo + per);
-    const long part_off = (long)chunk * rows;
+    const long kv0 = ((long)r.b * p.hk + r.hk) * p.n;   // first row of this kv head
 
-    const __bf16* qp = (const __bf16*)p.q + (((long)b * p.h + h) * p.nq + iq) * D;
-    const __bf16* kp = (const __bf16*)p.k + ((long)b * p.hk + hk) * p.n * D;
-    const __bf16* vp = (const __bf16*)p.v + ((long)b * p.hk + hk) * p.n * D;
-
-    // q in registers (fp32), replicated per lane as needed
-    float qreg[D];
-    #pragma unroll
-    for (int d = 0; d < D; ++d) qreg[d] = (float)qp[d];
-
-    // pass 1+2 fused online: each lane handles keys lane, lane+64, ...
-    float m = MASK_VALUE_F, l = 0.f;
-    float acc[D];
-    #pragma unroll
-    for (int d = 0; d < D; ++d) acc[d] = 0.f;
-
+    DecodeState<D> st;
+    st.init((const __bf16*)p.q + ((long)r.bh * p.nq + r.iq) * D);
     for (long j = j_lo + lane; j < j_hi; j += 64) {
-        const __bf16* krow = kp + j * D;
-        float s = 0.f;
-        #pragma unroll
-        for (int d = 0; d < D; d += 8) {
-            bf16x8 kv8 = *(const bf16x8*)(krow + d);
-            #pragma unroll
-            for (int e = 0; e < 8; ++e) s += qreg[d + e] * (float)kv8[e];
+        const long row = kv0 + j;
+        if constexpr (FP8) {
+            st.fold_fp8((const unsigned char*)p.k + row * D,
+                        (const unsigned char*)p.v + row * D,
+                        (const unsigned char*)p.kscale + row,
+                        (const unsigned char*)p.vscale + row, p.scale);
+        } else {
+            st.fold_bf16((const __bf16*)p.k + row * D, (const __bf16*)p.v + row * D,
+                         p.scale);
         }
-        s *= p.scale;
-        float m_new = fmaxf(m, s);
-        float alpha = __expf(m - m_new);
-        float w = __expf(s - m_new);
-        l = l * alpha + w;
-        const __bf16* vrow = vp + j * D;
-        #pragma unroll
-        for (int d = 0; d < D; d += 8) {
-            bf16x8 vv8 = *(const bf16x8*)(vrow + d);
-            #pragma unroll
-            for (int e = 0; e < 8; ++e) acc[d + e] = acc[d + e] * alpha + w * (float)vv8[e];
-        }
-        m = m_new;
     }
+    const long slot = (long)chunk * rows + (long)r.bh * p.nq + r.iq;
+    st.finish(lane, p.out + slot * D, p.lse + slot);
+}
 
-    // cross-lane merge (all 64 lanes -> lane 0's running stats)
-    #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        float m2 = __shfl_xor(m, off);
-        float l2 = __shfl_xor(l, off);
-        float m_new = fmaxf(m, m2);
-        float a1 = __expf(m - m_new), a2 = __expf(m2 - m_new);
-        l = l * a1 + l2 * a2;
-        #pragma unroll
-        for (int d = 0; d < D; ++d) {
-            float o2 = __shfl_xor(acc[d], off);
-            acc[d] = acc[d] * a1 + o2 * a2;
-        }
-        m = m_new;
-    }
-
-    float l_safe = fmaxf(l, 1e-38f);
-    if (lane == 0) {
-        float inv = 1.f / l_safe;
-        float* op = p.out + (part_off + (long)bh * p.nq + iq) * D;
-        #pragma unroll
-        for (int d = 0; d < D; ++d) op[d] = acc[d] * inv;
-        p.lse[part_off + (long)bh * p.nq + iq] = __logf(l_safe) + m;
+template <bool FP8>
+static void launch_decode_partial_t(const DecodeParams& p, int head_dim, hipStream_t stream) {
+    int waves = p.b * p.h * p.nq;
+    // the binding always sets p.chunks
+    long chunks = p.chunks > 0 ? p.chunks : decode_default_chunks(p.n, waves);
+    dim3 grid((waves + 3) / 4, (unsigned)chunks);
+    dim3 block(256);
+    if (head_dim == 64) {
+        hipLaunchKernelGGL((decode_partial_kernel<64, FP8>), grid, block, 0, stream, p);
+    } else if (head_dim == 128) {
+        hipLaunchKernelGGL((decode_partial_kernel<128, FP8>), grid, block, 0, stream, p);
+    } else {
+        __builtin_trap();
     }
 }
 
 void launch_decode_partial(const DecodeParams& p, int head_dim, hipStream_t stream) {
-    int waves = p.b * p.h * p.nq;
-    // kv-split fallback when the caller did not set p.chunks (the binding
-    // always does): mirror its GPU-swept heuristic — ~512 keys per wave,
-    // total waves capped near 8192, S capped at 256 (the chunk merge grows
-    // with S).  See bindings.cpp decode_partial.
-    long chunks = p.chunks > 0 ? p.chunks
-                 : max(1L, min(min((long)(p.n / 512 + 1), 256L),
-                               8192L / max((long)waves, 1L)));
-    dim3 grid((waves + 3) / 4, (unsigned)chunks);
-    dim3 block(256);
-    if (head_dim == 64) {
-        hipLaunchKernelGGL(decode_partial_kernel<64>, grid, block, 0, stream, p);
-    } else if (head_dim == 128) {
-        hipLaunchKernelGGL(decode_partial_kernel<128>, grid, block, 0, stream, p);
-    } else {
-        __builtin_trap();
-    }
-}
-
-
-// ---------------------------------------------------------------------------
-// FP8 KV-cache decode: same structure, 8-bit KV stream (half the HBM bytes —
-// decode is bandwidth-bound, measured 1.5-1.6 TB/s on the bf16 stream).
-// k8/v8 are e4m3 rows with ONE e8m0 scale per (kv row): the k scale folds
-// into the score (s_true = 2^ek * dot(q, k8)) and the v scale folds into the
-// softmax weight (acc += (w * 2^ev) * v8) — the inner loop does the same
-// fp32 math as the bf16 kernel, only the loads halve.  q stays bf16.
-// ---------------------------------------------------------------------------
-template <int D>
-__global__ __launch_bounds__(256) void decode_partial_fp8_kernel(DecodeParams p) {
-    const int rows = p.b * p.h * p.nq;
-    const int wave_global = (blockIdx.x * 4) + (threadIdx.x >> 6);
-    if (wave_global >= rows) return;
-    const int G = p.h / p.hk;
-    const int iq = wave_global % p.nq;
-    int r = wave_global / p.nq;
-    const int g = r % G;  r /= G;
-    const int hk = r % p.hk;
-    const int b = r / p.hk;
-    const int h = hk + g * p.hk;
-    const int bh = b * p.h + h;
-    const int lane = threadIdx.x & 63;
-    const int chunk = blockIdx.y;
-    const long per = (p.n + gridDim.y - 1) / gridDim.y;
-    const long j_lo = chunk * per;
-    const long j_hi = min(p.n, j_lo + per);
-    const long part_off = (long)chunk * rows;
-
-    const __bf16* qp = (const __bf16*)p.q + (((long)b * p.h + h) * p.nq + iq) * D;
-    const unsigned char* kp = (const unsigned char*)p.k + ((long)b * p.hk + hk) * p.n * D;
-    const unsigned char* vp = (const unsigned char*)p.v + ((long)b * p.hk + hk) * p.n * D;
-    const unsigned char* ksp = (const unsigned char*)p.kscale + ((long)b * p.hk + hk) * p.n;
-    const unsigned char* vsp = (const unsigned char*)p.vscale + ((long)b * p.hk + hk) * p.n;
-
-    float qreg[D];
-    #pragma unroll
-    for (int d = 0; d < D; ++d) qreg[d] = (float)qp[d];
-
-    float m = MASK_VALUE_F, l = 0.f;
-    float acc[D];
-    #pragma unroll
-    for (int d = 0; d < D; ++d) acc[d] = 0.f;
-
-    for (long j = j_lo + lane; j < j_hi; j += 64) {
-        const unsigned char* krow = kp + j * D;
-        float s = 0.f;
-        #pragma unroll
-        for (int d = 0; d < D; d += 16) {
-            uint4 k16 = *(const uint4*)(krow + d);
-            const unsigned* kw = (const unsigned*)&k16;
-            #pragma unroll
-            for (int w4 = 0; w4 < 4; ++w4) {
-                f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8(kw[w4], false);
-                f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8(kw[w4], true);
-                s += qreg[d + 4 * w4 + 0] * lo[0] + qreg[d + 4 * w4 + 1] * lo[1]
-                   + qreg[d + 4 * w4 + 2] * hi[0] + qreg[d + 4 * w4 + 3] * hi[1];
-            }
-        }
-        s *= p.scale * exp2f((float)ksp[j] - 127.f);
-        float m_new = fmaxf(m, s);
-        float alpha = __expf(m - m_new);
-        float w = __expf(s - m_new) * exp2f((float)vsp[j] - 127.f);
-        l = l * alpha + __expf(s - m_new);
-        const unsigned char* vrow = vp + j * D;
-        #pragma unroll
-        for (int d = 0; d < D; d += 16) {
-            uint4 v16 = *(const uint4*)(vrow + d);
-            const unsigned* vw = (const unsigned*)&v16;
-            #pragma unroll
-            for (int w4 = 0; w4 < 4; ++w4) {
-                f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8(vw[w4], false);
-                f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8(vw[w4], true);
-                int base = d + 4 * w4;
-                acc[base + 0] = acc[base + 0] * alpha + w * lo[0];
-                acc[base + 1] = acc[base + 1] * alpha + w * lo[1];
-                acc[base + 2] = acc[base + 2] * alpha + w * hi[0];
-                acc[base + 3] = acc[base + 3] * alpha + w * hi[1];
-            }
-        }
-        m = m_new;
-    }
-
-    #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        float m2 = __shfl_xor(m, off);
-        float l2 = __shfl_xor(l, off);
-        float m_new = fmaxf(m, m2);
-        float a1 = __expf(m - m_new), a2 = __expf(m2 - m_new);
-        l = l * a1 + l2 * a2;
-        #pragma unroll
-        for (int d = 0; d < D; ++d) {
-            float o2 = __shfl_xor(acc[d], off);
-            acc[d] = acc[d] * a1 + o2 * a2;
-        }
-        m = m_new;
-    }
-
-    float l_safe = fmaxf(l, 1e-38f);
-    if (lane == 0) {
-        float inv = 1.f / l_safe;
-        float* op = p.out + (part_off + (long)bh * p.nq + iq) * D;
-        #pragma unroll
-        for (int d = 0; d < D; ++d) op[d] = acc[d] * inv;
-        p.lse[part_off + (long)bh * p.nq + iq] = __logf(l_safe) + m;
-    }
+    launch_decode_partial_t<false>(p, head_dim, stream);
 }
 
 void launch_decode_partial_fp8(const DecodeParams& p, int head_dim, hipStream_t stream) {
-    int waves = p.b * p.h * p.nq;
-    // same swept kv-split fallback as launch_decode_partial
-    long chunks = p.chunks > 0 ? p.chunks
-                 : max(1L, min(min((long)(p.n / 512 + 1), 256L),
-                               8192L / max((long)waves, 1L)));
-    dim3 grid((waves + 3) / 4, (unsigned)chunks);
-    dim3 block(256);
-    if (head_dim == 64) {
-        hipLaunchKernelGGL(decode_partial_fp8_kernel<64>, grid, block, 0, stream, p);
-    } else if (head_dim == 128) {
-        hipLaunchKernelGGL(decode_partial_fp8_kernel<128>, grid, block, 0, stream, p);
-    } else {
-        __builtin_trap();
-    }
+    launch_decode_partial_t<true>(p, head_dim, stream);
 }
 
 

@@ -14,18 +14,15 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
-#include "attn_common.h"
+#include "decode_common.h"
 
 namespace ring_attn {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 template <int D, bool FP8, bool WIN>
 __global__ __launch_bounds__(256) void decode_partial_paged_kernel(PagedDecodeParams p) {
     // one wave per (b, q-head, query token); 4 waves per block; grid.y is
-    // the kv-split.  Same group-major wave->row mapping as decode.hip: the 4
-    // waves of a block cover the query tokens and then the GQA group-mates of
-    // ONE kv head, so their shared page stream is fetched once per XCD L2.
+    // the kv-split.  The wave->row mapping (decode_row) and the row body
+    // (DecodeState) are decode_common.h's, shared with the dense kernels.
     const int rows = p.b * p.h * p.nq;
     // grid = (row blocks, S) like the dense kernels.  With ragged lengths the
     // hardware's round-robin of consecutive workgroup ids over the 8 XCDs
@@ -40,16 +37,9 @@ __global__ __launch_bounds__(256) void decode_partial_paged_kernel(PagedDecodePa
     const int chunk = p.chunk_major ? (int)(lin % gridDim.y) : (int)blockIdx.y;
     const int wave_global = (row_block * 4) + (threadIdx.x >> 6);
     if (wave_global >= rows) return;
-    const int G = p.h / p.hk;
-    const int iq = wave_global % p.nq;
-    int r = wave_global / p.nq;
-    const int g = r % G;  r /= G;
-    const int hk = r % p.hk;           // reference tile GQA pairing
-    const int b = r / p.hk;
-    const int h = hk + g * p.hk;       // group-mate g of kv head hk
-    const int bh = b * p.h + h;
+    const DecodeRow r = decode_row(wave_global, p.h, p.hk, p.nq);
+    const int b = r.b, hk = r.hk, iq = r.iq;
     const int lane = threadIdx.x & 63;
-    const long part_off = (long)chunk * rows;
 
     // per-row key limit: the sequence's own length (never past what the
     // table can address); with `causal` the last nq cached positions are the
@@ -83,20 +73,12 @@ __global__ __launch_bounds__(256) void decode_partial_paged_kernel(PagedDecodePa
     const long j_lo = base + chunk * per;
     const long j_hi = (!WIN || lo < limit) ? min(limit, j_lo + per) : j_lo;
 
-    const __bf16* qp = (const __bf16*)p.q + (((long)b * p.h + h) * p.nq + iq) * D;
     const int* bt = p.block_table + (long)b * p.max_pages;
     const long pmask = (1L << shift) - 1;
     const bool uniform_page = shift >= 6;
 
-    // q in registers (fp32), replicated per lane as needed
-    float qreg[D];
-    #pragma unroll
-    for (int d = 0; d < D; ++d) qreg[d] = (float)qp[d];
-
-    float m = MASK_VALUE_F, l = 0.f;
-    float acc[D];
-    #pragma unroll
-    for (int d = 0; d < D; ++d) acc[d] = 0.f;
+    DecodeState<D> st;
+    st.init((const __bf16*)p.q + ((long)r.bh * p.nq + iq) * D);
 
     // each lane handles keys lane, lane+64, ...; the page id of the NEXT pass
     // is fetched before the current rows are consumed so the dependent
@@ -122,115 +104,35 @@ __global__ __launch_bounds__(256) void decode_partial_paged_kernel(PagedDecodePa
         // a page id outside the pool is never dereferenced
         if ((unsigned)pg < (unsigned)p.num_pages && (!WIN || j >= lo)) {
             const long row = ((((long)pg * p.hk + hk) << shift) | (j & pmask));
-            if constexpr (!FP8) {
-                const __bf16* krow = (const __bf16*)p.k_pages + row * D;
-                float s = 0.f;
-                #pragma unroll
-                for (int d = 0; d < D; d += 8) {
-                    bf16x8 kv8 = *(const bf16x8*)(krow + d);
-                    #pragma unroll
-                    for (int e = 0; e < 8; ++e) s += qreg[d + e] * (float)kv8[e];
-                }
-                s *= p.scale;
-                float m_new = fmaxf(m, s);
-                float alpha = __expf(m - m_new);
-                float w = __expf(s - m_new);
-                l = l * alpha + w;
-                const __bf16* vrow = (const __bf16*)p.v_pages + row * D;
-                #pragma unroll
-                for (int d = 0; d < D; d += 8) {
-                    bf16x8 vv8 = *(const bf16x8*)(vrow + d);
-                    #pragma unroll
-                    for (int e = 0; e < 8; ++e) acc[d + e] = acc[d + e] * alpha + w * (float)vv8[e];
-                }
-                m = m_new;
+            if constexpr (FP8) {
+                st.fold_fp8((const unsigned char*)p.k_pages + row * D,
+                            (const unsigned char*)p.v_pages + row * D,
+                            (const unsigned char*)p.kscale + row,
+                            (const unsigned char*)p.vscale + row, p.scale);
             } else {
-                // e4m3 rows with one e8m0 scale per row: the k scale folds
-                // into the score, the v scale into the softmax weight
-                const unsigned char* krow = (const unsigned char*)p.k_pages + row * D;
-                float s = 0.f;
-                #pragma unroll
-                for (int d = 0; d < D; d += 16) {
-                    uint4 k16 = *(const uint4*)(krow + d);
-                    const unsigned* kw = (const unsigned*)&k16;
-                    #pragma unroll
-                    for (int w4 = 0; w4 < 4; ++w4) {
-                        f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8(kw[w4], false);
-                        f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8(kw[w4], true);
-                        s += qreg[d + 4 * w4 + 0] * lo[0] + qreg[d + 4 * w4 + 1] * lo[1]
-                           + qreg[d + 4 * w4 + 2] * hi[0] + qreg[d + 4 * w4 + 3] * hi[1];
-                    }
-                }
-                s *= p.scale * exp2f((float)((const unsigned char*)p.kscale)[row] - 127.f);
-                float m_new = fmaxf(m, s);
-                float alpha = __expf(m - m_new);
-                float w = __expf(s - m_new)
-                        * exp2f((float)((const unsigned char*)p.vscale)[row] - 127.f);
-                l = l * alpha + __expf(s - m_new);
-                const unsigned char* vrow = (const unsigned char*)p.v_pages + row * D;
-                #pragma unroll
-                for (int d = 0; d < D; d += 16) {
-                    uint4 v16 = *(const uint4*)(vrow + d);
-                    const unsigned* vw = (const unsigned*)&v16;
-                    #pragma unroll
-                    for (int w4 = 0; w4 < 4; ++w4) {
-                        f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8(vw[w4], false);
-                        f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8(vw[w4], true);
-                        int base = d + 4 * w4;
-                        acc[base + 0] = acc[base + 0] * alpha + w * lo[0];
-                        acc[base + 1] = acc[base + 1] * alpha + w * lo[1];
-                        acc[base + 2] = acc[base + 2] * alpha + w * hi[0];
-                        acc[base + 3] = acc[base + 3] * alpha + w * hi[1];
-                    }
-                }
-                m = m_new;
+                st.fold_bf16((const __bf16*)p.k_pages + row * D,
+                             (const __bf16*)p.v_pages + row * D, p.scale);
             }
         }
         j = jn;
         pg = pg_next;
     }
 
-    // cross-lane merge (all 64 lanes -> lane 0's running stats)
-    #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        float m2 = __shfl_xor(m, off);
-        float l2 = __shfl_xor(l, off);
-        float m_new = fmaxf(m, m2);
-        float a1 = __expf(m - m_new), a2 = __expf(m2 - m_new);
-        l = l * a1 + l2 * a2;
-        #pragma unroll
-        for (int d = 0; d < D; ++d) {
-            float o2 = __shfl_xor(acc[d], off);
-            acc[d] = acc[d] * a1 + o2 * a2;
-        }
-        m = m_new;
-    }
-
-    // an empty chunk lands here with acc == 0, l == 0, m == MASK_VALUE_F and
-    // writes out = 0, lse = MASK_VALUE_F (the partial buffers are not
-    // zero-filled); decode_merge gives it weight exp(MASK - max) == 0
-    float l_safe = fmaxf(l, 1e-38f);
-    if (lane == 0) {
-        float inv = 1.f / l_safe;
-        float* op = p.out + (part_off + (long)bh * p.nq + iq) * D;
-        #pragma unroll
-        for (int d = 0; d < D; ++d) op[d] = acc[d] * inv;
-        p.lse[part_off + (long)bh * p.nq + iq] = __logf(l_safe) + m;
-    }
+    // an empty chunk still writes its partial (out = 0, lse = MASK_VALUE_F)
+    const long slot = (long)chunk * rows + (long)r.bh * p.nq + iq;
+    st.finish(lane, p.out + slot * D, p.lse + slot);
 }
 
 void launch_decode_partial_paged(const PagedDecodeParams& p, int head_dim, bool fp8,
                                  hipStream_t stream) {
     int waves = p.b * p.h * p.nq;
-    // same swept kv-split fallback as launch_decode_partial, driven by the
-    // host-known longest sequence (no device read on the step path)
+    // kv-split fallback (the binding always sets p.chunks), driven by the
+    // host-known longest sequence (no device read on the step path);
     // with a window the longest ROW SPAN drives the split, not the longest
     // sequence: win + 1 keys, nq - 1 more over the query tokens, up to 63 of
     // alignment in front
     const long span = p.has_win ? min(p.max_seq_len, p.win + p.nq + 63) : p.max_seq_len;
-    long chunks = p.chunks > 0 ? p.chunks
-                 : max(1L, min(min((long)(span / 512 + 1), 256L),
-                               8192L / max((long)waves, 1L)));
+    long chunks = p.chunks > 0 ? p.chunks : decode_default_chunks(span, waves);
     dim3 grid((waves + 3) / 4, (unsigned)chunks);
     dim3 block(256);
     // the window is a template switch: the unwindowed instantiations keep

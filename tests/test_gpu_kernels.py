@@ -577,6 +577,32 @@ def test_decode_partial_odd_shapes(h, hk, nq):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("n", [200, 77])
+def test_decode_partial_d128(n):
+    # the d 128 bf16 instantiation of the dense partial (the cases above are
+    # all d 64): GQA, nq 2, n no multiple of the lane stride, kv-split forced
+    # to 3 (n = 77: 26 keys per chunk, most lanes idle)
+    from ring_attention_amd.ops import hip_ext
+    b, h, hk, nq, d = 2, 4, 2, 2, 128
+    torch.manual_seed(47)
+    q = torch.randn(b, h, nq, d, device="cuda", dtype=torch.bfloat16)
+    k = torch.randn(b, hk, n, d, device="cuda", dtype=torch.bfloat16)
+    v = torch.randn(b, hk, n, d, device="cuda", dtype=torch.bfloat16)
+    ext = hip_ext.require()
+    outs, lses = ext.decode_partial(q, k, v, d ** -0.5, 3)
+    assert outs.shape == (3, b, h, nq, d)
+    out, lse = ext.decode_merge(outs, lses)
+    qc = q.float().cpu()
+    kc = k.float().cpu().repeat(1, h // hk, 1, 1)
+    vc = v.float().cpu().repeat(1, h // hk, 1, 1)
+    sim = torch.einsum("bhid,bhjd->bhij", qc, kc) * d ** -0.5
+    ref = torch.einsum("bhij,bhjd->bhid", sim.softmax(-1), vc)
+    err = (out.cpu() - ref).abs().max().item()
+    assert err < 3e-3, f"decode err {err}"
+    assert (lse.cpu() - sim.logsumexp(-1, keepdim=True)).abs().max().item() < 2e-3
+
+
+@pytest.mark.gpu
 def test_flash_attn_fp8():
     # MX-FP8 serving forward vs fp32 oracle.  Only the MFMA operands are
     # 8-bit (per-row e8m0 scales, P at unit scale); softmax/accum are fp32,
