@@ -384,6 +384,36 @@ struct PagedDecodeParams {
 void launch_decode_partial_paged(const PagedDecodeParams& p, int head_dim, bool fp8,
                                  hipStream_t stream);
 
+// Grouped paged decode (decode_paged_grouped.hip): the G * nq rows of one
+// (b, kv head) share one MFMA pass over the cache.  Row iq of sequence b sees
+// every key below P0 = seq_len - nq and key P0 + t iff bit t of
+// tree_bits[b][iq] (64 bits, low word first) is set; without tree_bits every
+// key below seq_len.
+struct PagedGroupedDecodeParams {
+    const void* q;          // bf16 (B, HQ, NQ, D)
+    const void* k_pages;    // bf16 or e4m3 bytes (P, HK, PS, D)
+    const void* v_pages;
+    const void* kscale;     // fp8 mode: e8m0 per row (P, HK, PS)
+    const void* vscale;
+    const int* block_table; // int32 (B, max_pages); entries at or beyond
+                            // ceil(seq_len / PS) are never read
+    const int* seq_lens;    // int32 (B); with tree_bits 0 or >= NQ (host-checked)
+    const int* tree_bits;   // int32 (B, NQ, 2) or null
+    float* out;             // fp32 (S, B, HQ, NQ, D) per-chunk partials
+    float* lse;             // fp32 (S, B, HQ, NQ, 1)
+    int b, h, hk, nq;       // h = HQ; q head qh reads kv head qh % hk
+    int page_shift, max_pages, num_pages;
+    int chunk_major;        // 1 = kv chunk is the fast workgroup index
+    float scale;
+    long chunks;            // kv-split S (0 = auto from max_seq_len)
+    long max_seq_len;       // host-known upper bound of seq_lens
+};
+
+// the kv-split S the launcher uses (the binding sizes the partials with it)
+long paged_grouped_chunks(const PagedGroupedDecodeParams& p);
+void launch_decode_partial_paged_grouped(const PagedGroupedDecodeParams& p, int head_dim,
+                                         bool fp8, hipStream_t stream);
+
 struct PagedAppendParams {
     const void* k_new;      // bf16 (B, HK, T, D)
     const void* v_new;      // bf16 (B, HK, T, D)

@@ -586,6 +586,60 @@ std::vector<at::Tensor> decode_partial_paged(
     return {r.out, r.lse};
 }
 
+std::vector<at::Tensor> decode_partial_paged_grouped(
+    at::Tensor q, at::Tensor k_pages, at::Tensor v_pages,
+    std::optional<at::Tensor> k_scales, std::optional<at::Tensor> v_scales,
+    at::Tensor block_table, at::Tensor seq_lens, int64_t max_seq_len,
+    double sm_scale, int64_t chunks_in, std::optional<at::Tensor> tree_bits) {
+    // operands as decode_partial_paged; tree_bits int32 (B,NQ,2): 64 mask
+    // bits per (sequence, draft), low word first (bit t = draft t visible).
+    // The caller has checked on the host that every sequence with a mask
+    // holds 0 or >= NQ tokens.  Same output contract as decode_partial.
+    CHECK_BF16_CONTIG(q);
+    TORCH_CHECK(q.dim() == 4, "q must be (B,HQ,NQ,D)");
+    const int64_t B = q.size(0), H = q.size(1), NQ = q.size(2), D = q.size(3);
+    bool fp8 = false;
+    const int shift = check_paged_pool(q, k_pages, v_pages, k_scales, v_scales,
+                                       block_table, seq_lens, B, D, &fp8);
+    const int64_t HK = k_pages.size(1);
+    TORCH_CHECK(H % HK == 0, "q heads must be a multiple of kv heads");
+    TORCH_CHECK(max_seq_len >= 0
+                && max_seq_len <= block_table.size(1) * k_pages.size(2),
+                "max_seq_len exceeds what block_table can address");
+    if (tree_bits.has_value()) {
+        TORCH_CHECK(NQ <= 64, "a tree mask covers at most 64 drafts");
+        TORCH_CHECK(tree_bits->scalar_type() == at::kInt && tree_bits->is_contiguous()
+                    && tree_bits->dim() == 3 && tree_bits->size(0) == B
+                    && tree_bits->size(1) == NQ && tree_bits->size(2) == 2
+                    && tree_bits->device() == q.device(),
+                    "tree_bits must be contiguous int32 (B,NQ,2) on q's device");
+    }
+    PagedGroupedDecodeParams p{};
+    p.b = (int)B; p.h = (int)H; p.hk = (int)HK; p.nq = (int)NQ;
+    p.chunks = chunks_in; p.max_seq_len = max_seq_len;
+    // the kv-split counts workgroups of 4 waves per (b, kv head, row tile),
+    // not one wave per row: the launcher's own figure sizes the partials
+    const int64_t S = B * H * NQ == 0 ? 1 : paged_grouped_chunks(p);
+    DecodePartials r = decode_partials(q, max_seq_len, S, sm_scale);
+    if (B * H * NQ == 0) return {r.out, r.lse};
+    p.chunks = r.chunks;
+    p.q = q.data_ptr();
+    p.k_pages = k_pages.data_ptr(); p.v_pages = v_pages.data_ptr();
+    if (fp8) { p.kscale = k_scales->data_ptr(); p.vscale = v_scales->data_ptr(); }
+    p.block_table = block_table.data_ptr<int>();
+    p.seq_lens = seq_lens.data_ptr<int>();
+    p.tree_bits = tree_bits.has_value() ? tree_bits->data_ptr<int>() : nullptr;
+    p.out = r.out.data_ptr<float>(); p.lse = r.lse.data_ptr<float>();
+    p.page_shift = shift;
+    p.max_pages = (int)block_table.size(1);
+    p.num_pages = (int)k_pages.size(0);
+    p.chunk_major = B > 1 ? 1 : 0;
+    p.scale = r.scale;
+    launch_decode_partial_paged_grouped(p, (int)D, fp8, at::hip::getCurrentHIPStream());
+    TORCH_CHECK(hipGetLastError() == hipSuccess, "grouped paged decode launch failed");
+    return {r.out, r.lse};
+}
+
 void paged_kv_append(
     at::Tensor k_new, at::Tensor v_new, at::Tensor k_pages, at::Tensor v_pages,
     std::optional<at::Tensor> k_scales, std::optional<at::Tensor> v_scales,
@@ -750,6 +804,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::arg("sm_scale") = -1.0, py::arg("causal") = false,
             py::arg("chunks") = 0, py::arg("has_win") = false,
             py::arg("win") = 0, py::arg("kv_after") = py::none());
+    mod.def("decode_partial_paged_grouped", &ring_attn::decode_partial_paged_grouped,
+            "CDNA4 grouped MFMA paged decode partial with an optional token-tree mask",
+            py::arg("q"), py::arg("k_pages"), py::arg("v_pages"),
+            py::arg("k_scales"), py::arg("v_scales"), py::arg("block_table"),
+            py::arg("seq_lens"), py::arg("max_seq_len"),
+            py::arg("sm_scale") = -1.0, py::arg("chunks") = 0,
+            py::arg("tree_bits") = py::none());
     mod.def("paged_kv_append", &ring_attn::paged_kv_append,
             "write new tokens into a paged KV cache (fused fp8 quantisation)",
             py::arg("k_new"), py::arg("v_new"), py::arg("k_pages"),

@@ -164,10 +164,58 @@ def _window_spans(lens: list[int], after: list[int], nq: int, causal: bool,
     return spans
 
 
+def _tree_visibility(tree_mask, grouped, causal: bool, window, cache, b: int,
+                     nq: int, device) -> tuple[bool, Tensor | None]:
+    """Checks the tree_mask / grouped arguments on the host (no device read)
+    and returns (the call takes the grouped kernel, its (b, nq, nq) bool
+    draft visibility or None for no mask).  `grouped=True, causal=True` is
+    the chain: the lower-triangular mask."""
+    name = "tree_attn_decode_paged"
+    if tree_mask is None and not grouped:
+        return False, None
+    if tree_mask is not None and grouped is False:
+        raise ValueError(f"{name}: tree_mask needs the grouped kernel (grouped=False given)")
+    if tree_mask is not None and causal:
+        raise ValueError(f"{name}: tree_mask and causal=True exclude each other "
+                         "(a chain is the lower-triangular mask)")
+    if window is not None or any(cache.host_starts):
+        raise ValueError(f"{name}: the grouped kernel serves neither a window nor a "
+                         "cache with released pages")
+    if tree_mask is None and not causal:
+        return True, None
+    if nq > 64:
+        raise ValueError(f"{name}: a tree mask covers at most 64 drafts (nq = {nq})")
+    if any(0 < n < nq for n in cache.host_lens):
+        raise ValueError(f"{name}: a masked sequence holds 0 or at least nq = {nq} tokens")
+    if tree_mask is None:
+        vis = torch.ones(nq, nq, dtype=torch.bool, device=device).tril()
+    else:
+        vis = tree_mask.to(device=device, dtype=torch.bool)
+    if vis.dim() == 2:
+        vis = vis[None].expand(b, nq, nq)
+    if tuple(vis.shape) != (b, nq, nq):
+        raise ValueError(f"{name}: tree_mask must be (nq, nq) or (b, nq, nq)")
+    if not bool(vis.diagonal(dim1=-2, dim2=-1).all()):
+        raise ValueError(f"{name}: every draft attends itself (tree_mask diagonal)")
+    return True, vis
+
+
+def _tree_bits(vis: Tensor) -> Tensor:
+    """(b, nq, nq) bool -> int32 (b, nq, 2): bit t of the 64-bit row word
+    (low word first) = draft t visible."""
+    b, nq, _ = vis.shape
+    w = torch.zeros(b, nq, 64, dtype=torch.int64, device=vis.device)
+    w[..., :nq] = vis
+    pw = torch.tensor([1 << t for t in range(32)], dtype=torch.int64, device=vis.device)
+    words = (w.view(b, nq, 2, 32) * pw).sum(-1)             # unsigned 32-bit values
+    return torch.where(words >= 1 << 31, words - (1 << 32), words).to(torch.int32).contiguous()
+
+
 def _local_paged_decode_partial(q: Tensor, cache, causal: bool = False,
                                 use_hip_kernel: bool | None = None,
                                 chunks: int = 0, window: int | None = None,
-                                kv_after=None) -> tuple[Tensor, Tensor]:
+                                kv_after=None, tree_mask: Tensor | None = None,
+                                grouped: bool | None = None) -> tuple[Tensor, Tensor]:
     """Local flash-decode partial over a PagedKVCache:
     (out fp32 (b,h,nq,d), lse fp32 (b,h,nq,1)).
 
@@ -186,10 +234,19 @@ def _local_paged_decode_partial(q: Tensor, cache, causal: bool = False,
     A cache that has released pages (`release_prefix`) is only served with a
     window whose rows all start at or beyond `cache.host_starts`; anything
     else raises ValueError before a kernel is launched.
+
+    `tree_mask` (bool (b, nq, nq) or (nq, nq)) replaces the chain-shaped tail:
+    the last nq cached tokens are the drafts, tree_mask[i, t] lets draft i
+    attend draft t (key seq_len - nq + t), and every draft attends the whole
+    prefix below seq_len - nq.  It runs the grouped MFMA kernel
+    (csrc/decode_paged_grouped.hip), as does `grouped=True` with `causal`
+    either way; see tree_attn_decode_paged for the rules.
     """
     b, h, nq, d = q.shape
     assert b == cache.max_seqs and d == cache.dim_head
     assert h % cache.kv_heads == 0
+    use_grouped, vis = _tree_visibility(tree_mask, grouped, causal, window, cache,
+                                        b, nq, q.device)
     if window is not None and window < 0:
         raise ValueError("tree_attn_decode_paged: window must be >= 0")
     after = None
@@ -215,6 +272,14 @@ def _local_paged_decode_partial(q: Tensor, cache, causal: bool = False,
         kd = cache.kernel_dim
         import torch.nn.functional as _F
         qb = _F.pad(q, (0, kd - d)) if d != kd else q
+        if use_grouped:
+            outs, lses = ext.decode_partial_paged_grouped(
+                qb.to(torch.bfloat16).contiguous(),
+                cache.k_pages, cache.v_pages, cache.k_scales, cache.v_scales,
+                cache.block_table, cache.seq_lens, cache.max_seq_len,
+                d ** -0.5, chunks, None if vis is None else _tree_bits(vis))
+            out, lse = ext.decode_merge(outs, lses)
+            return (out[..., :d] if d != kd else out), lse
         outs, lses = ext.decode_partial_paged(
             qb.to(torch.bfloat16).contiguous(),
             cache.k_pages, cache.v_pages, cache.k_scales, cache.v_scales,
@@ -245,7 +310,11 @@ def _local_paged_decode_partial(q: Tensor, cache, causal: bool = False,
         kf = kf.float().repeat(groups, 1, 1)            # tile pairing qh % hk
         vf = vf.float().repeat(groups, 1, 1)
         sim = torch.einsum("hid,hjd->hij", q[i].float(), kf) * scale
-        if causal:
+        if vis is not None:                             # prefix open, drafts by mask
+            masked = torch.zeros(nq, n, dtype=torch.bool, device=q.device)
+            masked[:, n - nq:] = ~vis[i]
+            sim = sim.masked_fill(masked[None], float("-inf"))
+        elif causal:
             limit = n - (nq - 1 - torch.arange(nq, device=q.device))
             masked = torch.arange(n, device=q.device)[None, :] >= limit[:, None]
             sim = sim.masked_fill(masked[None], float("-inf"))
@@ -271,6 +340,8 @@ def tree_attn_decode_paged(
     use_hip_kernel: bool | None = None,
     window: int | None = None,
     kv_after=None,
+    tree_mask: Tensor | None = None,
+    grouped: bool | None = None,
 ) -> Tensor:
     """Tree-attention decode over a paged KV cache with per-sequence lengths.
 
@@ -291,7 +362,23 @@ def tree_attn_decode_paged(
     weight 0.  A cache that has released pages (`PagedKVCache.release_prefix`)
     must be served with a window that stays at or beyond its released prefix;
     otherwise ValueError is raised before anything runs.
+
+    `tree_mask` verifies a TREE of drafts in one step (Medusa / EAGLE /
+    SpecInfer style): a bool tensor (b, nq, nq), or (nq, nq) shared by the
+    batch, where tree_mask[i, t] lets draft i attend draft t, the token cached
+    at seq_len - nq + t.  Every draft attends the whole prefix below
+    seq_len - nq; the diagonal must be True; nq <= 64; every sequence holds
+    at least nq tokens or none (an empty slot returns dead rows).  It runs the
+    grouped MFMA kernel, which stacks the (group-mate, draft) rows of a kv
+    head into 32-row tiles and streams K/V once per tile.  Only the rank
+    that holds the tail passes it.  `grouped=True` takes that kernel without
+    a mask too (`causal=True` is then the chain, the lower-triangular mask);
+    `grouped=None` takes it exactly when tree_mask is given.  tree_mask with
+    causal=True, with grouped=False, or either with `window` or a cache that
+    has released pages raises ValueError before anything runs, as does a
+    violated rule above (lengths come from the host mirrors).
     """
     local_out, lse = _local_paged_decode_partial(q, cache, causal, use_hip_kernel,
-                                                 window=window, kv_after=kv_after)
+                                                 window=window, kv_after=kv_after,
+                                                 tree_mask=tree_mask, grouped=grouped)
     return _merge_across_ranks(local_out, lse, q.dtype, eps)

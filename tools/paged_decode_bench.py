@@ -20,8 +20,13 @@ attends W + 1 of them), bf16 and fp8, every page size, alternating in the same
 rounds.  `vs_short` is windowed / short.  `--only-window` skips the dense
 groups.
 
+`--grouped NQ [NQ ...]` times the grouped MFMA kernel (`grouped=True`) against
+the row kernel of the same build on one sequence with NQ query tokens per
+head, bf16 and fp8, page size 64, shuffled table, alternating in the same
+rounds, and returns; `vs_row` is grouped / row.
+
     python tools/paged_decode_bench.py [--kv-len 131072] [--rounds 7] [--out F]
-        [--window 1024 4096 32768] [--only-window]
+        [--window 1024 4096 32768] [--only-window] [--grouped 1 4 16]
 """
 
 from __future__ import annotations
@@ -116,6 +121,9 @@ def main():
                          "against an unwindowed step over window + 1 keys")
     ap.add_argument("--only-window", action="store_true",
                     help="skip the dense-vs-paged groups")
+    ap.add_argument("--grouped", type=int, nargs="*", default=[],
+                    help="query tokens per head: time grouped=True against the "
+                         "row kernel (ps 64, shuffled) and nothing else")
     ap.add_argument("--out", default=None, help="also write the records here (JSON)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "paged_decode_bench needs a GPU"
@@ -151,6 +159,21 @@ def main():
     q = torch.randn(1, h, 1, d, device=dev, dtype=bf)
     k = torch.randn(1, hk, n, d, device=dev, dtype=bf)
     v = torch.randn(1, hk, n, d, device=dev, dtype=bf)
+
+    # ---- grouped MFMA kernel vs the row kernel ------------------------------
+    for nq in args.grouped:
+        qn = torch.randn(1, h, nq, d, device=dev, dtype=bf)
+        for fp8 in (False, True):
+            cache = PagedKVCache.from_dense(k, v, [n], 64, fp8=fp8, shuffle_seed=7)
+            steps = {"row": lambda c=cache: _local_paged_decode_partial(qn, c),
+                     "grouped": lambda c=cache: _local_paged_decode_partial(
+                         qn, c, grouped=True)}
+            err = (steps["grouped"]()[0] - steps["row"]()[0]).abs().max().item()
+            assert err < 5e-3, (nq, fp8, err)
+            run_group(f"{'fp8' if fp8 else 'bf16'} b=1 kv={n} {h}q/{hk}kv nq={nq}",
+                      steps, args, results, base_of=lambda label: "row", ratio="vs_row")
+    if args.grouped:
+        return write(args, results)
 
     # ---- sliding window: kv-len cached, window w, vs w + 1 keys cached -----
     for w in args.window:
