@@ -496,6 +496,40 @@ struct Fp8FwdParams : Fp8FwdCore {
 
 void launch_attn_fwd_fp8(const Fp8FwdParams& p, int head_dim, hipStream_t stream);
 
+// Operand quantisation (quantize_fp8.hip): bf16/fp16 -> e4m3 + e8m0 in one
+// launch.  A row segment quantises rows (b, i, hh) of a strided input whose
+// last dim is contiguous (element (b, i, hh, c) at b*sb + i*sn + hh*sh + c)
+// into contiguous (B, n_pad, H, D) bytes; rows i >= n and columns c >= d are
+// zeros.  Scales are per (row, 64-column chunk), or per whole row in the
+// KV-cache form.
+struct QuantRowSeg {
+    const void* x;          // bf16 / fp16
+    void* out8;             // e4m3 bytes (B, n_pad, H, D)
+    void* scales;           // e8m0 (B, n_pad, H, D/64); cache form (B, n_pad, H)
+    long sb, sn, sh;        // input strides in elements, multiples of 8
+    int b, n, n_pad, h;
+    unsigned blocks;        // workgroups of this segment (set by the launcher)
+};
+
+struct QuantFp8Params {
+    QuantRowSeg row[2];     // q and k; cache form: k and v
+    // V: (B, Nk, HK, d) strided -> v8t (B, HK, D, nk_pad) e4m3 with one scale
+    // per (d row, 64-key chunk), vs (B, HK, D, nk_pad / 64).  Unused (null) in
+    // the cache form.
+    const void* v;
+    void* v8t;
+    void* vs;
+    long vsb, vsn, vsh;     // input strides in elements, multiples of 8
+    int b, hk, nk, nk_pad;  // nk_pad % 64 == 0
+    int d;                  // true head dim: d <= D, d % 8 == 0
+    unsigned v_tiles;       // key tiles per (b, kv head) (set by the launcher)
+};
+
+// head_dim = D in {64, 128}; fp16 selects the input type; row_scale the
+// KV-cache form (no V job)
+void launch_quantize_fp8(QuantFp8Params p, int head_dim, bool fp16, bool row_scale,
+                         hipStream_t stream);
+
 struct RotaryParams {
     const void* x;      // bf16 (B, N, H, D)
     const float* cos_t; // fp32 (N, D/2) host-precomputed table

@@ -422,6 +422,97 @@ std::vector<at::Tensor> attn_fwd_fp8(at::Tensor q8, at::Tensor k8, at::Tensor v8
     return {out, lse};
 }
 
+// a quantiser input: bf16/fp16 on the GPU, contiguous last dim, and 16-byte
+// row loads possible everywhere (base address and every stride)
+static void check_quant_input(const at::Tensor& t, at::ScalarType dtype, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.dim() == 4 && t.scalar_type() == dtype
+                && (dtype == at::kBFloat16 || dtype == at::kHalf),
+                name, " must be a 4-d bf16/fp16 GPU tensor (q, k, v of one dtype)");
+    TORCH_CHECK(t.numel() > 0, name, " must not be empty");
+    TORCH_CHECK(t.stride(3) == 1 && t.size(3) % 8 == 0, name,
+                ": last dim must be contiguous and a multiple of 8");
+    for (int i = 0; i < 3; ++i)     // the stride of a size-1 dim is never used
+        TORCH_CHECK(t.size(i) == 1 || (t.stride(i) >= 0 && t.stride(i) % 8 == 0),
+                    name, ": strides must be multiples of 8 elements");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+                name, ": data must be 16-byte aligned");
+}
+
+// the caller's output buffer (checked) or a fresh one
+static at::Tensor quant_output(const std::optional<std::vector<at::Tensor>>& out, size_t idx,
+                               at::IntArrayRef shape, const at::Tensor& like) {
+    if (!out.has_value()) return at::empty(shape, like.options().dtype(at::kByte));
+    const at::Tensor& t = (*out)[idx];
+    TORCH_CHECK(t.scalar_type() == at::kByte && t.is_contiguous() && t.device() == like.device()
+                && t.sizes() == shape,
+                "out[", idx, "] must be contiguous uint8 of shape ", shape, " on the inputs' device");
+    return t;
+}
+
+std::vector<at::Tensor> quantize_fp8(at::Tensor q, at::Tensor k, at::Tensor v, int64_t d_kernel,
+                                     std::optional<std::vector<at::Tensor>> out) {
+    // q (B,Nq,H,d), k/v (B,Nk,HK,d) bf16/fp16, any b/n/h strides -> the
+    // operands of attn_fwd_fp8 at head dim D = d_kernel >= d (zero-filled):
+    //   q8 (B,nq_pad,H,D), k8 (B,nk_pad,HK,D), v8t (B,HK,D,nk_pad) e4m3;
+    //   qs (B,nq_pad,H,D/64), ks (B,nk_pad,HK,D/64), vs (B,HK,D,nk_pad/64) e8m0;
+    // q rows padded to 256, kv rows to 128.  One launch.
+    const auto dtype = q.scalar_type();
+    check_quant_input(q, dtype, "q"); check_quant_input(k, dtype, "k");
+    check_quant_input(v, dtype, "v");
+    const int64_t B = q.size(0), NQ = q.size(1), H = q.size(2), d = q.size(3);
+    const int64_t NK = k.size(1), HK = k.size(2), D = d_kernel;
+    TORCH_CHECK(D == 64 || D == 128, "d_kernel must be 64 or 128");
+    TORCH_CHECK(d <= D, "head dim ", d, " exceeds d_kernel ", D);
+    TORCH_CHECK(k.size(0) == B && k.size(3) == d && v.sizes() == k.sizes()
+                && k.device() == q.device() && v.device() == q.device(),
+                "k/v must be (B,Nk,HK,d) on q's device");
+    const int64_t nq_pad = (NQ + 255) / 256 * 256, nk_pad = (NK + 127) / 128 * 128;
+    TORCH_CHECK(B * nq_pad * H * (D / 64) < (int64_t(1) << 31)
+                && B * nk_pad * HK * (D / 64) < (int64_t(1) << 31), "quantize_fp8: too many rows");
+    TORCH_CHECK(!out.has_value() || out->size() == 6, "out must hold 6 tensors");
+    auto q8 = quant_output(out, 0, {B, nq_pad, H, D}, q);
+    auto k8 = quant_output(out, 1, {B, nk_pad, HK, D}, q);
+    auto v8t = quant_output(out, 2, {B, HK, D, nk_pad}, q);
+    auto qs = quant_output(out, 3, {B, nq_pad, H, D / 64}, q);
+    auto ks = quant_output(out, 4, {B, nk_pad, HK, D / 64}, q);
+    auto vs = quant_output(out, 5, {B, HK, D, nk_pad / 64}, q);
+    QuantFp8Params p{};
+    p.row[0] = {q.data_ptr(), q8.data_ptr(), qs.data_ptr(), q.stride(0), q.stride(1),
+                q.stride(2), (int)B, (int)NQ, (int)nq_pad, (int)H, 0u};
+    p.row[1] = {k.data_ptr(), k8.data_ptr(), ks.data_ptr(), k.stride(0), k.stride(1),
+                k.stride(2), (int)B, (int)NK, (int)nk_pad, (int)HK, 0u};
+    p.v = v.data_ptr(); p.v8t = v8t.data_ptr(); p.vs = vs.data_ptr();
+    p.vsb = v.stride(0); p.vsn = v.stride(1); p.vsh = v.stride(2);
+    p.b = (int)B; p.hk = (int)HK; p.nk = (int)NK; p.nk_pad = (int)nk_pad; p.d = (int)d;
+    launch_quantize_fp8(p, (int)D, dtype == at::kHalf, false, at::hip::getCurrentHIPStream());
+    TORCH_CHECK(hipGetLastError() == hipSuccess, "quantize_fp8 launch failed");
+    return {q8, k8, v8t, qs, ks, vs};
+}
+
+std::vector<at::Tensor> quantize_kv_cache(at::Tensor k, at::Tensor v) {
+    // k, v (B,HK,N,D) contiguous bf16/fp16, D in {64, 128} -> k8/v8 (B,HK,N,D)
+    // e4m3 with one e8m0 scale per row, ks/vs (B,HK,N).  One launch.
+    const auto dtype = k.scalar_type();
+    check_quant_input(k, dtype, "k"); check_quant_input(v, dtype, "v");
+    TORCH_CHECK(k.is_contiguous() && v.is_contiguous() && v.sizes() == k.sizes()
+                && v.device() == k.device(), "k/v must be contiguous (B,HK,N,D) on one device");
+    const int64_t B = k.size(0), HK = k.size(1), N = k.size(2), D = k.size(3);
+    TORCH_CHECK(D == 64 || D == 128, "head dim must be 64 or 128");
+    const int64_t rows = B * HK * N;
+    TORCH_CHECK(rows < (int64_t(1) << 31), "quantize_kv_cache: too many rows");
+    auto opt = k.options().dtype(at::kByte);
+    auto k8 = at::empty({B, HK, N, D}, opt), v8 = at::empty({B, HK, N, D}, opt);
+    auto ks = at::empty({B, HK, N}, opt), vs = at::empty({B, HK, N}, opt);
+    QuantFp8Params p{};
+    // the cache is one flat run of rows: (1, rows, 1, D)
+    p.row[0] = {k.data_ptr(), k8.data_ptr(), ks.data_ptr(), 0, D, 0, 1, (int)rows, (int)rows, 1, 0u};
+    p.row[1] = {v.data_ptr(), v8.data_ptr(), vs.data_ptr(), 0, D, 0, 1, (int)rows, (int)rows, 1, 0u};
+    p.d = (int)D;
+    launch_quantize_fp8(p, (int)D, dtype == at::kHalf, true, at::hip::getCurrentHIPStream());
+    TORCH_CHECK(hipGetLastError() == hipSuccess, "quantize_kv_cache launch failed");
+    return {k8, v8, ks, vs};
+}
+
 std::vector<at::Tensor> decode_partial_fp8(at::Tensor q, at::Tensor k8, at::Tensor v8,
                                            at::Tensor ks, at::Tensor vs,
                                            double sm_scale, int64_t chunks_in) {
@@ -790,6 +881,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::arg("causal") = false, py::arg("nk_true") = 0,
             py::arg("diag") = 0, py::arg("q_stride") = 1,
             py::arg("has_win") = false, py::arg("win") = 0);
+    mod.def("quantize_fp8", &ring_attn::quantize_fp8,
+            "bf16/fp16 q, k, v -> the MX-FP8 forward's operands (one launch)",
+            py::arg("q"), py::arg("k"), py::arg("v"), py::arg("d_kernel"),
+            py::arg("out") = py::none());
+    mod.def("quantize_kv_cache", &ring_attn::quantize_kv_cache,
+            "bf16/fp16 (B,HK,N,D) KV cache -> e4m3 + per-row e8m0 (one launch)",
+            py::arg("k"), py::arg("v"));
     mod.def("decode_partial_fp8", &ring_attn::decode_partial_fp8,
             "CDNA4 FP8 KV-cache decode partial",
             py::arg("q"), py::arg("k8"), py::arg("v8"), py::arg("ks"),

@@ -15,6 +15,7 @@
 #include <hip/hip_bf16.h>
 
 #include "decode_common.h"
+#include "fp8_quant.h"
 
 namespace ring_attn {
 
@@ -213,22 +214,12 @@ __global__ __launch_bounds__(256) void paged_kv_append_kernel(PagedAppendParams 
         #pragma unroll
         for (int off = 16; off > 0; off >>= 1)         // stays inside the half-wave
             amax = fmaxf(amax, __shfl_xor(amax, off));
-        // e = ceil(log2(max(amax, 2^-126) / 448)), integer-exact: with
-        // amax = mant * 2^ex (mant in [1, 2)) and 448 = 1.75 * 2^8 this is
-        // ex - 8 when mant <= 1.75 and ex - 7 otherwise; zero / subnormal
-        // amax clamps to 2^-126 and lands on the lower clamp below
-        const unsigned bits = __float_as_uint(amax);
-        const int ex = (int)((bits >> 23) & 0xffu);
-        const unsigned mant = bits & 0x7fffffu;
-        int e = ex == 0 ? -127 : ex - 127 - 8 + (mant > 0x600000u ? 1 : 0);
-        e = min(max(e, -127), 127);
-        #pragma unroll
-        for (int i = 0; i < 4; ++i) x[i] = ldexpf(x[i], -e);   // exact power-of-two scaling
-        int u = __builtin_amdgcn_cvt_pk_fp8_f32(x[0], x[1], 0, false);
-        u = __builtin_amdgcn_cvt_pk_fp8_f32(x[2], x[3], u, true);
+        // the project's one scale rule and exact scaling (fp8_quant.h)
+        const int e = e8m0_exponent(amax);
+        const unsigned u = e4m3_pack4(x[0], x[1], x[2], x[3], e);
         if (act) {
             unsigned char* dst = (unsigned char*)(is_v ? p.v_pages : p.k_pages) + drow * D;
-            *(unsigned*)(dst + sl * 4) = (unsigned)u;
+            *(unsigned*)(dst + sl * 4) = u;
         }
         if (sl == 0) {
             unsigned char* sc = (unsigned char*)(is_v ? p.vscale : p.kscale);

@@ -41,6 +41,7 @@ a valid e4m3, never NaN) while the kernel masks at the true kv length.
 from __future__ import annotations
 
 import math
+import os
 
 import torch
 from torch import Tensor
@@ -69,8 +70,8 @@ def _pad_dim(x: Tensor, dim: int, mult: int) -> Tensor:
     return torch.cat((x, x.new_zeros(shape)), dim=dim).contiguous()
 
 
-def quantize_fp8(q: Tensor, k: Tensor, v: Tensor):
-    """Quantize (b, n, h, d) q/k/v for attn_fwd_fp8.
+def _quantize_fp8_torch(q: Tensor, k: Tensor, v: Tensor):
+    """The format's definition as a torch chain (CPU, fp32 inputs, A/B).
 
     Returns (q8, k8, v8t, qs, ks, vs) uint8 views, PADDED to the kernel's
     tile alignment (q rows to 256, kv rows to 128) with zero bytes and
@@ -105,6 +106,65 @@ def quantize_fp8(q: Tensor, k: Tensor, v: Tensor):
             vs_b.contiguous())
 
 
+def _fused_quant(*xs: Tensor) -> bool:
+    """True where the HIP quantiser serves these inputs: bf16/fp16 of one
+    dtype on the GPU.  CPU and fp32 inputs take the torch chain, and so does
+    everything under RING_ATTN_NO_FUSED_QUANT=1 (read per call: the A/B
+    switch of tools/fp8_quantize_bench.py and the tests)."""
+    return (all(x.is_cuda and x.dtype == xs[0].dtype and x.numel() > 0 for x in xs)
+            and xs[0].dtype in (torch.bfloat16, torch.float16)
+            and not os.environ.get("RING_ATTN_NO_FUSED_QUANT"))
+
+
+def _row_loadable(x: Tensor) -> Tensor:
+    """x as the kernel can read it with 16-byte row loads: contiguous last
+    dim, every other stride a multiple of 8 elements, 16-byte aligned data.
+    Slices of a fused projection qualify as they are; anything else is copied."""
+    ok = (x.stride(-1) == 1 and x.data_ptr() % 16 == 0
+          and all(n == 1 or (s >= 0 and s % 8 == 0)
+                  for n, s in zip(x.shape[:-1], x.stride()[:-1])))
+    return x if ok else x.contiguous()
+
+
+def quantize_fp8(q: Tensor, k: Tensor, v: Tensor, out=None):
+    """Quantize (b, n, h, d) q/k/v for attn_fwd_fp8, d <= 128.
+
+    Returns (q8, k8, v8t, qs, ks, vs) uint8, PADDED to the kernel's tile
+    alignment (q rows to 256, kv rows to 128) and to the kernel head dim
+    D = 64 (d <= 64) or 128 with zero bytes and scale 2^-127 — zero is a valid
+    e4m3 (never NaN), and the kernel masks scores at the true kv length:
+      q8/k8 (b, n_pad, h, D) e4m3; v8t (b, hk, D, nk_pad) e4m3;
+      qs/ks (b, n_pad, h, D // 64) e8m0; vs (b, hk, D, nk_pad // 64) e8m0.
+    bf16/fp16 GPU inputs with d % 8 == 0 are quantized by ONE HIP launch
+    (csrc/quantize_fp8.hip) that reads q/k/v through their own strides; other
+    inputs take the torch chain `_quantize_fp8_torch`, the format's
+    definition.  `out`, six uint8 tensors of the shapes above, is filled and
+    returned instead of fresh buffers (serving reuses them across calls).
+    """
+    d = q.shape[-1]
+    if d <= 128 and d % 8 == 0 and _fused_quant(q, k, v):
+        res = hip_ext.require().quantize_fp8(
+            _row_loadable(q), _row_loadable(k), _row_loadable(v),
+            64 if d <= 64 else 128, list(out) if out is not None else None)
+        return tuple(res)
+    if d % 64 != 0:
+        # exact zero-pad to the next kernel dim ({64, 128}, like the bf16
+        # path's _pad_head_dim): padded q/k dims contribute 0 to scores,
+        # padded v dims are sliced off by the caller
+        kd = 64 if d < 64 else 128
+        assert d <= 128, "fp8 path: head dim <= 128"
+        import torch.nn.functional as F
+        q = F.pad(q, (0, kd - d))
+        k = F.pad(k, (0, kd - d))
+        v = F.pad(v, (0, kd - d))
+    res = _quantize_fp8_torch(q, k, v)
+    if out is None:
+        return res
+    for o, r in zip(out, res):
+        o.copy_(r)
+    return tuple(out)
+
+
 @torch.no_grad()
 def flash_attn_fp8(
     q: Tensor, k: Tensor, v: Tensor,
@@ -123,16 +183,9 @@ def flash_attn_fp8(
     """
     d = q.shape[-1]
     sm = sm_scale if sm_scale is not None else d ** -0.5
-    if d % 64 != 0:
-        # exact zero-pad to the next kernel dim ({64, 128}, like the bf16
-        # path's _pad_head_dim): padded q/k dims contribute 0 to scores,
-        # padded v dims are sliced off below
-        kd = 64 if d < 64 else 128
-        assert d <= 128, "fp8 path: head dim <= 128"
-        import torch.nn.functional as F
-        q = F.pad(q, (0, kd - d))
-        k = F.pad(k, (0, kd - d))
-        v = F.pad(v, (0, kd - d))
+    # a head dim below the kernel's {64, 128} comes back zero-padded from the
+    # quantiser (exact: padded q/k dims add 0 to the scores) and the padded v
+    # dims are sliced off below
     q8, k8, v8t, qs, ks, vs = quantize_fp8(q, k, v)
     out, lse = flash_attn_fp8_quantized(
         q8, k8, v8t, qs, ks, vs, sm,
@@ -287,8 +340,17 @@ def quantize_kv_cache(k: Tensor, v: Tensor):
     Returns (k8, v8, ks, vs) uint8: k8/v8 (b, hk, n, d), ks/vs (b, hk, n).
     Halves the decode kernel's HBM stream (decode is bandwidth-bound); the
     scales fold into the score / softmax weight, so the decode math is the
-    same fp32 online softmax.  Quantize once at cache-write time.
+    same fp32 online softmax.  Quantize once at cache-write time: one HIP
+    launch for bf16/fp16 GPU caches of head dim 64 or 128 (the row form of
+    csrc/quantize_fp8.hip), the torch chain otherwise.
     """
+    if k.shape[-1] in (64, 128) and k.shape == v.shape and _fused_quant(k, v):
+        return tuple(hip_ext.require().quantize_kv_cache(k.contiguous(), v.contiguous()))
+    return _quantize_kv_cache_torch(k, v)
+
+
+def _quantize_kv_cache_torch(k: Tensor, v: Tensor):
+    """quantize_kv_cache's definition as a torch chain."""
     kf, vf = k.float(), v.float()
     ks_b, ks_s = _e8m0(kf.abs().amax(dim=-1))
     vs_b, vs_s = _e8m0(vf.abs().amax(dim=-1))

@@ -25,6 +25,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "attn_fwd_v2.hip"),
         os.path.join(CSRC, "attn_fwd_fp8.hip"),
         os.path.join(CSRC, "attn_fwd_paged.hip"),
+        os.path.join(CSRC, "quantize_fp8.hip"),
         os.path.join(CSRC, "attn_bwd.hip"),
         os.path.join(CSRC, "decode.hip"),
         os.path.join(CSRC, "decode_paged.hip"),
