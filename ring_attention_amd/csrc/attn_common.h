@@ -407,6 +407,13 @@ struct PagedGroupedDecodeParams {
     float scale;
     long chunks;            // kv-split S (0 = auto from max_seq_len)
     long max_seq_len;       // host-known upper bound of seq_lens
+    // lookback window (PagedDecodeParams' definition): row (b, iq) sits at
+    // seq_len + kv_after[b] - nq + iq and attends keys
+    // [clamp(position - window, 0, limit), limit); with tree_bits the mask is
+    // the chain (host-checked), so limit = seq_len - (nq - 1 - iq)
+    int has_window;         // 0 = no window (window and kv_after unused)
+    long window;            // >= 0
+    const int* kv_after;    // int32 (B): tokens held by LATER ranks, or null (0)
 };
 
 // the kv-split S the launcher uses (the binding sizes the partials with it)

@@ -681,11 +681,14 @@ std::vector<at::Tensor> decode_partial_paged_grouped(
     at::Tensor q, at::Tensor k_pages, at::Tensor v_pages,
     std::optional<at::Tensor> k_scales, std::optional<at::Tensor> v_scales,
     at::Tensor block_table, at::Tensor seq_lens, int64_t max_seq_len,
-    double sm_scale, int64_t chunks_in, std::optional<at::Tensor> tree_bits) {
+    double sm_scale, int64_t chunks_in, std::optional<at::Tensor> tree_bits,
+    bool has_window, int64_t window, std::optional<at::Tensor> kv_after) {
     // operands as decode_partial_paged; tree_bits int32 (B,NQ,2): 64 mask
     // bits per (sequence, draft), low word first (bit t = draft t visible).
     // The caller has checked on the host that every sequence with a mask
-    // holds 0 or >= NQ tokens.  Same output contract as decode_partial.
+    // holds 0 or >= NQ tokens, and that a mask under a window is the chain.
+    // has_window / window / kv_after as in decode_partial_paged.  Same output
+    // contract as decode_partial.
     CHECK_BF16_CONTIG(q);
     TORCH_CHECK(q.dim() == 4, "q must be (B,HQ,NQ,D)");
     const int64_t B = q.size(0), H = q.size(1), NQ = q.size(2), D = q.size(3);
@@ -705,9 +708,20 @@ std::vector<at::Tensor> decode_partial_paged_grouped(
                     && tree_bits->device() == q.device(),
                     "tree_bits must be contiguous int32 (B,NQ,2) on q's device");
     }
+    TORCH_CHECK(!has_window || (window >= 0 && window < (int64_t(1) << 40)),
+                "window must lie in [0, 2^40)");
+    if (has_window && kv_after.has_value()) {
+        TORCH_CHECK(kv_after->scalar_type() == at::kInt && kv_after->is_contiguous()
+                    && kv_after->dim() == 1 && kv_after->size(0) == B
+                    && kv_after->device() == q.device(),
+                    "kv_after must be contiguous int32 (B,) on q's device");
+    }
     PagedGroupedDecodeParams p{};
     p.b = (int)B; p.h = (int)H; p.hk = (int)HK; p.nq = (int)NQ;
     p.chunks = chunks_in; p.max_seq_len = max_seq_len;
+    p.has_window = has_window ? 1 : 0;
+    p.window = has_window ? window : 0;
+    p.kv_after = has_window && kv_after.has_value() ? kv_after->data_ptr<int>() : nullptr;
     // the kv-split counts workgroups of 4 waves per (b, kv head, row tile),
     // not one wave per row: the launcher's own figure sizes the partials
     const int64_t S = B * H * NQ == 0 ? 1 : paged_grouped_chunks(p);
@@ -908,7 +922,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::arg("k_scales"), py::arg("v_scales"), py::arg("block_table"),
             py::arg("seq_lens"), py::arg("max_seq_len"),
             py::arg("sm_scale") = -1.0, py::arg("chunks") = 0,
-            py::arg("tree_bits") = py::none());
+            py::arg("tree_bits") = py::none(), py::arg("has_window") = false,
+            py::arg("window") = 0, py::arg("kv_after") = py::none());
     mod.def("paged_kv_append", &ring_attn::paged_kv_append,
             "write new tokens into a paged KV cache (fused fp8 quantisation)",
             py::arg("k_new"), py::arg("v_new"), py::arg("k_pages"),

@@ -35,6 +35,19 @@
 //     below ceil(len / page_size) are read, an id outside the pool is never
 //     dereferenced, and rows at or beyond the chunk's end are zero-filled
 //     without forming an address (0 * NaN would poison the MFMA).
+//   * window (WIN): row iq's query sits at qpos = len + kv_after[b] - nq + iq
+//     and attends keys [lo, limit), lo = clamp(qpos - window, 0, limit)
+//     (tree_decode.py's _window_spans; with tree_bits the mask is the chain,
+//     host-checked, so limit = P0 + iq + 1).  lo never decreases in iq:
+//     lo_min (row 0) and lo_max (row nq - 1) are wave-uniform.  The workgroup
+//     splits [lo_min & ~127, len) instead of [0, len), so blocks stay
+//     32-aligned and passes 128-aligned; a wave drops the blocks that end at
+//     or below lo_min, and a block is open only from lo_max up: below it the
+//     masked arm also tests key >= the lane's own lo.  Pages below the one
+//     that holds lo_min may be released: a 16-key half with no key at or
+//     above lo_min reads no table entry and is zero-filled (every element
+//     there is masked anyway).  A sequence whose row 0 is dead has only dead
+//     rows and touches neither the table nor the pool.
 //   * mask: with tree_bits the last nq cached keys are the drafts' own
 //     tokens; key P0 + t (P0 = len - nq) is visible to draft iq iff bit t of
 //     tree_bits[b][iq] is set, keys below P0 to every row.  Only blocks that
@@ -109,7 +122,7 @@ __device__ __forceinline__ GroupedChunk<FP8> grouped_pool_chunk(
 
 }  // namespace
 
-template <int D, bool FP8>
+template <int D, bool FP8, bool WIN>
 __global__ __launch_bounds__(GWAVES * 64)
 void decode_partial_paged_grouped_kernel(PagedGroupedDecodeParams p) {
     static_assert(D == 64 || D == 128);
@@ -147,10 +160,27 @@ void decode_partial_paged_grouped_kernel(PagedGroupedDecodeParams p) {
     const long len = min(max((long)__builtin_amdgcn_readfirstlane(p.seq_lens[b]), 0L),
                          (long)p.max_pages << shift);
     const long P0 = p.tree_bits ? max(len - p.nq, 0L) : len;
-    long per = (len + gridDim.y - 1) / gridDim.y;
+    // window (WIN): qp0 = row 0's qpos - window; the rows' lower bounds run
+    // from lo_min (row 0) to lo_max (row nq - 1).  Row 0 dead <=> every row
+    // dead (the chain's limit and qpos both grow by one per row; without a
+    // mask the limit is len for all).  The unwindowed instantiation keeps
+    // base = 0 as a constant.
+    long qp0 = 0, lo_min = 0, lo_max = 0;
+    bool live = true;
+    if constexpr (WIN) {
+        const long after = p.kv_after
+            ? (long)__builtin_amdgcn_readfirstlane(p.kv_after[b]) : 0L;
+        qp0 = len + after - p.nq - p.window;
+        const long lim0 = p.tree_bits ? min(len, P0 + 1) : len;
+        lo_min = min(max(qp0, 0L), lim0);
+        lo_max = min(max(qp0 + p.nq - 1, 0L), len);
+        live = lo_min < lim0;
+    }
+    const long base = lo_min & ~(long)(GPASS - 1);
+    long per = (len - base + gridDim.y - 1) / gridDim.y;
     per = (per + GPASS - 1) & ~(long)(GPASS - 1);
-    const long j_lo = (long)chunk * per;
-    const long j_hi = min(len, j_lo + per);
+    const long j_lo = base + (long)chunk * per;
+    const long j_hi = live ? min(len, j_lo + per) : j_lo;
 
     // ---- this lane's row: q fragments and mask word.  Rows past R run on
     // row 0 and are dropped in the epilogue.
@@ -167,6 +197,10 @@ void decode_partial_paged_grouped_kernel(PagedGroupedDecodeParams p) {
         const int* tb = p.tree_bits + ((long)b * p.nq + iq) * 2;
         bits = (unsigned long long)(unsigned)tb[0] | ((unsigned long long)(unsigned)tb[1] << 32);
     }
+    // this row's lower bound as a draft index (key - P0); the draft test
+    // below supplies the row's limit
+    int tl = 0;
+    if constexpr (WIN) tl = (int)(min(max(qp0 + iq, 0L), len) - P0);
 
     float m_run = MASK_VALUE_F;
     float l_run = 0.f;
@@ -185,7 +219,10 @@ void decode_partial_paged_grouped_kernel(PagedGroupedDecodeParams p) {
 
     // ids of the pages that hold keys [j0, j0 + 16) and [j0 + 16, j0 + 32)
     int pg_a = -1, pg_b = -1;
-    auto table_id = [&](long j) { return j < j_hi ? bt[j >> shift] : -1; };
+    // (WIN: a half that ends at or below lo_min may lie in a released page)
+    auto table_id = [&](long j) {
+        return j < j_hi && (!WIN || j + 16 > lo_min) ? bt[j >> shift] : -1;
+    };
     auto load_block = [&](long j0, int id_a, int id_b) {
         auto pool_row = [&](long j, bool& ok) {
             // bit select: written as ?: the two ids become a table in
@@ -232,6 +269,8 @@ void decode_partial_paged_grouped_kernel(PagedGroupedDecodeParams p) {
 
     const float scale2 = p.scale * LOG2E;
     long j0 = j_lo + wid * GTILE;
+    // lo_min < base + GPASS: only the first pass holds blocks below lo_min
+    if constexpr (WIN) if (j0 + GTILE <= lo_min) j0 += GPASS;
     if (j0 < j_hi) {
         load_block(j0, table_id(j0), table_id(j0 + 16));
         pg_a = table_id(j0 + GPASS);
@@ -262,7 +301,7 @@ void decode_partial_paged_grouped_kernel(PagedGroupedDecodeParams p) {
 
         // ---- scale, mask.  A block below P0 is visible to every row and
         // keeps raw scores (the scale folds into the exp argument).
-        const bool open_block = j0 + GTILE <= P0;
+        const bool open_block = j0 + GTILE <= P0 && (!WIN || j0 >= lo_max);
         float smax = MASK_VALUE_F;
         if (open_block) {
             #pragma unroll
@@ -274,7 +313,8 @@ void decode_partial_paged_grouped_kernel(PagedGroupedDecodeParams p) {
             #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int t = t0 + (r & 3) + 8 * (r >> 2);
-                const bool ok = t < 0 || (t < nt && ((bits >> (t & 63)) & 1));
+                const bool ok = (!WIN || t >= tl)
+                                && (t < 0 || (t < nt && ((bits >> (t & 63)) & 1)));
                 const float x = ok ? s[r] * scale2 : MASK_VALUE_F;
                 s[r] = x;
                 smax = fmaxf(smax, x);
@@ -400,8 +440,12 @@ void decode_partial_paged_grouped_kernel(PagedGroupedDecodeParams p) {
 
 long paged_grouped_chunks(const PagedGroupedDecodeParams& p) {
     const long tiles = ((long)(p.h / p.hk) * p.nq + GTILE - 1) / GTILE;
+    // with a window the longest workgroup span drives the split: window + 1
+    // keys, nq - 1 more over the rows, up to GPASS - 1 of alignment in front
+    const long span = p.has_window ? std::min(p.max_seq_len, p.window + p.nq + GPASS - 1)
+                                   : p.max_seq_len;
     return p.chunks > 0 ? p.chunks
-                        : decode_default_chunks(p.max_seq_len, GWAVES * p.b * p.hk * tiles);
+                        : decode_default_chunks(span, GWAVES * p.b * p.hk * tiles);
 }
 
 void launch_decode_partial_paged_grouped(const PagedGroupedDecodeParams& p, int head_dim,
@@ -409,16 +453,28 @@ void launch_decode_partial_paged_grouped(const PagedGroupedDecodeParams& p, int 
     const long tiles = ((long)(p.h / p.hk) * p.nq + GTILE - 1) / GTILE;
     dim3 grid((unsigned)(p.b * p.hk * tiles), (unsigned)paged_grouped_chunks(p));
     dim3 block(GWAVES * 64);
+    // the window is a template switch: the unwindowed instantiations keep
+    // the code they had before the window existed
+#define LAUNCH_GROUPED(D_, FP8_)                                                        \
+    do {                                                                                \
+        if (p.has_window)                                                               \
+            hipLaunchKernelGGL((decode_partial_paged_grouped_kernel<D_, FP8_, true>),   \
+                               grid, block, 0, stream, p);                              \
+        else                                                                            \
+            hipLaunchKernelGGL((decode_partial_paged_grouped_kernel<D_, FP8_, false>),  \
+                               grid, block, 0, stream, p);                              \
+    } while (0)
     if (head_dim == 64 && !fp8)
-        hipLaunchKernelGGL((decode_partial_paged_grouped_kernel<64, false>), grid, block, 0, stream, p);
+        LAUNCH_GROUPED(64, false);
     else if (head_dim == 128 && !fp8)
-        hipLaunchKernelGGL((decode_partial_paged_grouped_kernel<128, false>), grid, block, 0, stream, p);
+        LAUNCH_GROUPED(128, false);
     else if (head_dim == 64)
-        hipLaunchKernelGGL((decode_partial_paged_grouped_kernel<64, true>), grid, block, 0, stream, p);
+        LAUNCH_GROUPED(64, true);
     else if (head_dim == 128)
-        hipLaunchKernelGGL((decode_partial_paged_grouped_kernel<128, true>), grid, block, 0, stream, p);
+        LAUNCH_GROUPED(128, true);
     else
         __builtin_trap();
+#undef LAUNCH_GROUPED
 }
 
 }  // namespace ring_attn

@@ -178,9 +178,9 @@ def _tree_visibility(tree_mask, grouped, causal: bool, window, cache, b: int,
     if tree_mask is not None and causal:
         raise ValueError(f"{name}: tree_mask and causal=True exclude each other "
                          "(a chain is the lower-triangular mask)")
-    if window is not None or any(cache.host_starts):
-        raise ValueError(f"{name}: the grouped kernel serves neither a window nor a "
-                         "cache with released pages")
+    if tree_mask is not None and (window is not None or any(cache.host_starts)):
+        raise ValueError(f"{name}: a tree mask serves neither a window nor a cache "
+                         "with released pages (a draft's position is its depth)")
     if tree_mask is None and not causal:
         return True, None
     if nq > 64:
@@ -240,7 +240,9 @@ def _local_paged_decode_partial(q: Tensor, cache, causal: bool = False,
     attend draft t (key seq_len - nq + t), and every draft attends the whole
     prefix below seq_len - nq.  It runs the grouped MFMA kernel
     (csrc/decode_paged_grouped.hip), as does `grouped=True` with `causal`
-    either way; see tree_attn_decode_paged for the rules.
+    either way; see tree_attn_decode_paged for the rules.  `grouped=True`
+    takes `window` / `kv_after` and a released cache with the meaning above
+    (the kernel's windowed variant); `tree_mask` takes neither.
     """
     b, h, nq, d = q.shape
     assert b == cache.max_seqs and d == cache.dim_head
@@ -272,22 +274,23 @@ def _local_paged_decode_partial(q: Tensor, cache, causal: bool = False,
         kd = cache.kernel_dim
         import torch.nn.functional as _F
         qb = _F.pad(q, (0, kd - d)) if d != kd else q
+        win_args = (window is not None, 0 if window is None else int(window),
+                    None if window is None or after is None else
+                    torch.tensor(after, dtype=torch.int32).to(q.device))
         if use_grouped:
             outs, lses = ext.decode_partial_paged_grouped(
                 qb.to(torch.bfloat16).contiguous(),
                 cache.k_pages, cache.v_pages, cache.k_scales, cache.v_scales,
                 cache.block_table, cache.seq_lens, cache.max_seq_len,
-                d ** -0.5, chunks, None if vis is None else _tree_bits(vis))
+                d ** -0.5, chunks, None if vis is None else _tree_bits(vis),
+                *win_args)
             out, lse = ext.decode_merge(outs, lses)
             return (out[..., :d] if d != kd else out), lse
         outs, lses = ext.decode_partial_paged(
             qb.to(torch.bfloat16).contiguous(),
             cache.k_pages, cache.v_pages, cache.k_scales, cache.v_scales,
             cache.block_table, cache.seq_lens, cache.max_seq_len,
-            d ** -0.5, causal, chunks, window is not None,
-            0 if window is None else int(window),
-            None if window is None or after is None else
-            torch.tensor(after, dtype=torch.int32).to(q.device))
+            d ** -0.5, causal, chunks, *win_args)
         out, lse = ext.decode_merge(outs, lses)
         if d != kd:
             out = out[..., :d]
@@ -373,10 +376,12 @@ def tree_attn_decode_paged(
     head into 32-row tiles and streams K/V once per tile.  Only the rank
     that holds the tail passes it.  `grouped=True` takes that kernel without
     a mask too (`causal=True` is then the chain, the lower-triangular mask);
-    `grouped=None` takes it exactly when tree_mask is given.  tree_mask with
-    causal=True, with grouped=False, or either with `window` or a cache that
-    has released pages raises ValueError before anything runs, as does a
-    violated rule above (lengths come from the host mirrors).
+    `grouped=None` takes it exactly when tree_mask is given.  `grouped=True`
+    without a tree_mask serves `window` / `kv_after` and a cache with released
+    pages exactly as the row kernel does.  tree_mask with causal=True, with
+    grouped=False, with `window` or with a cache that has released pages
+    raises ValueError before anything runs, as does a violated rule above
+    (lengths come from the host mirrors).
     """
     local_out, lse = _local_paged_decode_partial(q, cache, causal, use_hip_kernel,
                                                  window=window, kv_after=kv_after,

@@ -23,7 +23,8 @@ groups.
 `--grouped NQ [NQ ...]` times the grouped MFMA kernel (`grouped=True`) against
 the row kernel of the same build on one sequence with NQ query tokens per
 head, bf16 and fp8, page size 64, shuffled table, alternating in the same
-rounds, and returns; `vs_row` is grouped / row.
+rounds, and returns; `vs_row` is grouped / row.  With `--window` both kernels
+take `window=W` over the `--kv-len` cached keys, one group per W.
 
     python tools/paged_decode_bench.py [--kv-len 131072] [--rounds 7] [--out F]
         [--window 1024 4096 32768] [--only-window] [--grouped 1 4 16]
@@ -165,13 +166,16 @@ def main():
         qn = torch.randn(1, h, nq, d, device=dev, dtype=bf)
         for fp8 in (False, True):
             cache = PagedKVCache.from_dense(k, v, [n], 64, fp8=fp8, shuffle_seed=7)
-            steps = {"row": lambda c=cache: _local_paged_decode_partial(qn, c),
-                     "grouped": lambda c=cache: _local_paged_decode_partial(
-                         qn, c, grouped=True)}
-            err = (steps["grouped"]()[0] - steps["row"]()[0]).abs().max().item()
-            assert err < 5e-3, (nq, fp8, err)
-            run_group(f"{'fp8' if fp8 else 'bf16'} b=1 kv={n} {h}q/{hk}kv nq={nq}",
-                      steps, args, results, base_of=lambda label: "row", ratio="vs_row")
+            for w in args.window or [None]:
+                steps = {"row": lambda c=cache, w=w: _local_paged_decode_partial(
+                             qn, c, window=w),
+                         "grouped": lambda c=cache, w=w: _local_paged_decode_partial(
+                             qn, c, window=w, grouped=True)}
+                err = (steps["grouped"]()[0] - steps["row"]()[0]).abs().max().item()
+                assert err < 5e-3, (nq, fp8, w, err)
+                run_group(f"{'fp8' if fp8 else 'bf16'} b=1 kv={n} {h}q/{hk}kv nq={nq}"
+                          + ("" if w is None else f" window={w}"),
+                          steps, args, results, base_of=lambda label: "row", ratio="vs_row")
     if args.grouped:
         return write(args, results)
 
