@@ -421,6 +421,34 @@ long paged_grouped_chunks(const PagedGroupedDecodeParams& p);
 void launch_decode_partial_paged_grouped(const PagedGroupedDecodeParams& p, int head_dim,
                                          bool fp8, hipStream_t stream);
 
+// Grouped decode over the dense cache (decode_grouped.hip): DecodeParams'
+// layouts, the grouped paged kernel's rows and mask.  Row iq sees every key
+// below P0 = n - nq and key P0 + t iff bit t of tree_bits[b][iq] is set;
+// without tree_bits every key below n.
+struct GroupedDecodeParams {
+    const void* q;          // bf16 (B, HQ, NQ, D)
+    const void* k;          // bf16 or e4m3 bytes (B, HK, N, D)
+    const void* v;
+    const void* kscale;     // fp8 mode: e8m0 per kv row (B, HK, N)
+    const void* vscale;
+    const int* tree_bits;   // int32 (B, NQ, 2) or null; needs n >= NQ (host-checked)
+    float* out;             // fp32 (S, B, HQ, NQ, D) per-chunk partials
+    float* lse;             // fp32 (S, B, HQ, NQ, 1)
+    int b, h, hk, nq;       // h = HQ; q head qh reads kv head qh % hk
+    int chunk_major;        // 1 = kv chunk is the fast workgroup index
+    int tiles_cap;          // most row tiles per workgroup (0 = the launcher's limit)
+    float scale;
+    long n;
+    long chunks;            // kv-split S (0 = auto from n)
+};
+
+// row tiles per workgroup and the kv-split S the launcher uses (the binding
+// sizes the partials with the latter)
+int grouped_decode_tiles(const GroupedDecodeParams& p, int head_dim);
+long grouped_decode_chunks(const GroupedDecodeParams& p, int head_dim);
+void launch_decode_partial_grouped(const GroupedDecodeParams& p, int head_dim, bool fp8,
+                                   hipStream_t stream);
+
 struct PagedAppendParams {
     const void* k_new;      // bf16 (B, HK, T, D)
     const void* v_new;      // bf16 (B, HK, T, D)

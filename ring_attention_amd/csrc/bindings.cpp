@@ -745,6 +745,67 @@ std::vector<at::Tensor> decode_partial_paged_grouped(
     return {r.out, r.lse};
 }
 
+std::vector<at::Tensor> decode_partial_grouped(
+    at::Tensor q, at::Tensor k, at::Tensor v,
+    std::optional<at::Tensor> kscale, std::optional<at::Tensor> vscale,
+    double sm_scale, int64_t chunks_in, std::optional<at::Tensor> tree_bits) {
+    // q bf16 (B,HQ,NQ,D); k, v (B,HK,N,D) bf16, or e4m3 bytes with e8m0 row
+    // scales kscale / vscale (B,HK,N); tree_bits int32 (B,NQ,2) as in
+    // decode_partial_paged_grouped: the last NQ keys are the drafts.  Same
+    // output contract as decode_partial.
+    CHECK_BF16_CONTIG(q);
+    TORCH_CHECK(q.dim() == 4 && k.dim() == 4, "q must be (B,HQ,NQ,D), k and v (B,HK,N,D)");
+    const int64_t B = q.size(0), H = q.size(1), NQ = q.size(2), D = q.size(3);
+    const int64_t HK = k.size(1), N = k.size(2);
+    const bool fp8 = k.scalar_type() == at::kByte;
+    TORCH_CHECK(fp8 == kscale.has_value() && fp8 == vscale.has_value(),
+                "uint8 (fp8) k / v come with kscale and vscale, bf16 k / v without");
+    if (fp8) {
+        for (auto* t : {&k, &v, &*kscale, &*vscale})
+            TORCH_CHECK(t->scalar_type() == at::kByte && t->is_contiguous()
+                        && t->device() == q.device(),
+                        "fp8 cache operands must be contiguous uint8 on q's device");
+        TORCH_CHECK(kscale->numel() == B * HK * N && vscale->numel() == B * HK * N,
+                    "kscale / vscale must be (B,HK,N)");
+    } else {
+        CHECK_BF16_CONTIG(k); CHECK_BF16_CONTIG(v);
+    }
+    TORCH_CHECK(k.sizes() == v.sizes() && k.size(0) == B && k.size(3) == D,
+                "k and v must both be (B,HK,N,D)");
+    TORCH_CHECK(D == 64 || D == 128, "head dim must be 64 or 128");
+    TORCH_CHECK(HK > 0 && H % HK == 0, "q heads must be a multiple of kv heads");
+    if (tree_bits.has_value()) {
+        TORCH_CHECK(NQ <= 64, "a tree mask covers at most 64 drafts");
+        TORCH_CHECK(N >= NQ, "a masked cache holds at least NQ keys");
+        TORCH_CHECK(tree_bits->scalar_type() == at::kInt && tree_bits->is_contiguous()
+                    && tree_bits->dim() == 3 && tree_bits->size(0) == B
+                    && tree_bits->size(1) == NQ && tree_bits->size(2) == 2
+                    && tree_bits->device() == q.device(),
+                    "tree_bits must be contiguous int32 (B,NQ,2) on q's device");
+    }
+    GroupedDecodeParams p{};
+    p.b = (int)B; p.h = (int)H; p.hk = (int)HK; p.nq = (int)NQ; p.n = N;
+    p.chunks = chunks_in;
+    // RING_ATTN_GROUPED_TILES=1|2|4 sets the most row tiles a workgroup
+    // shares (A/B; unset: the launcher's own limit)
+    const char* cap = std::getenv("RING_ATTN_GROUPED_TILES");
+    p.tiles_cap = cap ? std::atoi(cap) : 0;
+    // the kv-split counts workgroups, as in decode_partial_paged_grouped
+    const int64_t S = B * H * NQ == 0 ? 1 : grouped_decode_chunks(p, (int)D);
+    DecodePartials r = decode_partials(q, N, S, sm_scale);
+    if (B * H * NQ == 0) return {r.out, r.lse};
+    p.chunks = r.chunks;
+    p.q = q.data_ptr(); p.k = k.data_ptr(); p.v = v.data_ptr();
+    if (fp8) { p.kscale = kscale->data_ptr(); p.vscale = vscale->data_ptr(); }
+    p.tree_bits = tree_bits.has_value() ? tree_bits->data_ptr<int>() : nullptr;
+    p.out = r.out.data_ptr<float>(); p.lse = r.lse.data_ptr<float>();
+    p.chunk_major = B > 1 ? 1 : 0;
+    p.scale = r.scale;
+    launch_decode_partial_grouped(p, (int)D, fp8, at::hip::getCurrentHIPStream());
+    TORCH_CHECK(hipGetLastError() == hipSuccess, "grouped decode launch failed");
+    return {r.out, r.lse};
+}
+
 void paged_kv_append(
     at::Tensor k_new, at::Tensor v_new, at::Tensor k_pages, at::Tensor v_pages,
     std::optional<at::Tensor> k_scales, std::optional<at::Tensor> v_scales,
@@ -924,6 +985,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::arg("sm_scale") = -1.0, py::arg("chunks") = 0,
             py::arg("tree_bits") = py::none(), py::arg("has_window") = false,
             py::arg("window") = 0, py::arg("kv_after") = py::none());
+    mod.def("decode_partial_grouped", &ring_attn::decode_partial_grouped,
+            "CDNA4 grouped MFMA decode partial over the dense cache (bf16 or fp8), "
+            "optional token-tree mask",
+            py::arg("q"), py::arg("k"), py::arg("v"),
+            py::arg("kscale") = py::none(), py::arg("vscale") = py::none(),
+            py::arg("sm_scale") = -1.0, py::arg("chunks") = 0,
+            py::arg("tree_bits") = py::none());
     mod.def("paged_kv_append", &ring_attn::paged_kv_append,
             "write new tokens into a paged KV cache (fused fp8 quantisation)",
             py::arg("k_new"), py::arg("v_new"), py::arg("k_pages"),

@@ -26,8 +26,15 @@ from .parallel import get_rank, get_world_size, is_distributed
 
 
 def _local_decode_partial(q: Tensor, k: Tensor, v: Tensor,
-                          use_hip_kernel: bool | None = None) -> tuple[Tensor, Tensor]:
-    """Local flash-decode partial: (out fp32 (b,h,nq,dv), lse fp32 (b,h,nq,1))."""
+                          use_hip_kernel: bool | None = None,
+                          vis: Tensor | None = None,
+                          grouped: bool = False) -> tuple[Tensor, Tensor]:
+    """Local flash-decode partial: (out fp32 (b,h,nq,dv), lse fp32 (b,h,nq,1)).
+
+    `vis` ((b, nq, nq) bool, from _draft_visibility) makes the last nq keys
+    the drafts' own tokens: row i attends key n - nq + t iff vis[:, i, t], and
+    every key below n - nq.  `grouped` (implied by `vis`) takes the grouped
+    MFMA kernel (csrc/decode_grouped.hip) instead of the row kernel."""
     if q.is_cuda and use_hip_kernel is not False:
         from .ops import hip_ext
         if hip_ext.available():
@@ -38,11 +45,19 @@ def _local_decode_partial(q: Tensor, k: Tensor, v: Tensor,
             qb = _F.pad(q, (0, kd - d)) if d != kd else q
             kb = _F.pad(k, (0, kd - d)) if d != kd else k
             vb = _F.pad(v, (0, kd - dv)) if dv != kd else v
-            outs, lses = hip_ext.decode_partial(
-                qb.to(torch.bfloat16).contiguous(),
-                kb.to(torch.bfloat16).contiguous(),
-                vb.to(torch.bfloat16).contiguous(),
-                sm_scale=d ** -0.5)
+            if grouped or vis is not None:
+                outs, lses = hip_ext.require().decode_partial_grouped(
+                    qb.to(torch.bfloat16).contiguous(),
+                    kb.to(torch.bfloat16).contiguous(),
+                    vb.to(torch.bfloat16).contiguous(),
+                    None, None, d ** -0.5, 0,
+                    None if vis is None else _tree_bits(vis))
+            else:
+                outs, lses = hip_ext.decode_partial(
+                    qb.to(torch.bfloat16).contiguous(),
+                    kb.to(torch.bfloat16).contiguous(),
+                    vb.to(torch.bfloat16).contiguous(),
+                    sm_scale=d ** -0.5)
             # fused S-chunk merge (the torch reduce expression costs more
             # dispatches than the decode kernel itself at S = 256)
             out, lse = hip_ext.require().decode_merge(outs, lses)
@@ -56,10 +71,48 @@ def _local_decode_partial(q: Tensor, k: Tensor, v: Tensor,
         kf = kf.repeat(1, groups, 1, 1)
         vf = vf.repeat(1, groups, 1, 1)
     sim = torch.einsum("bhid,bhjd->bhij", q.float(), kf) * scale
+    if vis is not None:                 # prefix open, drafts by mask (diagonal set)
+        nq, n = q.shape[2], k.shape[2]
+        masked = torch.zeros(q.shape[0], nq, n, dtype=torch.bool, device=q.device)
+        masked[:, :, n - nq:] = ~vis
+        sim = sim.masked_fill(masked[:, None], float("-inf"))
     lse = sim.logsumexp(dim=-1, keepdim=True)
     attn = torch.softmax(sim, dim=-1)
     out = torch.einsum("bhij,bhjd->bhid", attn, vf)
     return out, lse
+
+
+def _dense_visibility(name: str, tree_mask, grouped, causal: bool, b: int, nq: int,
+                      n: int | None, device, here: bool = True
+                      ) -> tuple[bool, Tensor | None]:
+    """The dense entry points' routing: (the call takes the grouped kernel,
+    its (b, nq, nq) draft visibility or None).  `n`: keys this rank holds
+    (None: none).  `here=False`: the arguments are checked but the mask
+    belongs to another rank, and this one runs the grouped kernel unmasked."""
+    _check_mask_args(name, tree_mask, grouped, causal)
+    if causal and grouped is False:
+        raise ValueError(f"{name}: causal needs the grouped kernel (grouped=False given): "
+                         "the row kernel has no key limit per row")
+    if tree_mask is None and not causal:
+        return bool(grouped), None
+    if here and (n is None or n < nq):
+        raise ValueError(f"{name}: a masked call needs at least nq = {nq} keys on the "
+                         f"rank that holds the tail")
+    vis = _draft_visibility(name, tree_mask, [], b, nq, device)
+    return True, vis if here else None
+
+
+def _tail_shard(n: int, world: int, nq: int, name: str) -> int:
+    """Rank that holds the last chunk of `k.chunk(world, dim=-2)` over n keys
+    (the drafts' own tokens).  That chunk must hold all nq of them: ValueError
+    otherwise, from shapes alone, so on every rank."""
+    size = -(-n // world) if n else 0
+    tail = -(-n // size) - 1 if size else 0
+    last = n - tail * size
+    if last < nq:
+        raise ValueError(f"{name}: the last kv shard holds {last} keys, fewer than "
+                         f"nq = {nq}: the drafts' tokens must lie on one rank")
+    return tail
 
 
 @torch.no_grad()
@@ -70,25 +123,56 @@ def tree_attn_decode(
     eps: float = 1e-8,
     shard_kv_seq: bool = True,
     use_hip_kernel: bool | None = None,
+    causal: bool = False,
+    tree_mask: Tensor | None = None,
+    grouped: bool | None = None,
 ) -> Tensor:
+    """Tree-attention decode of q (b, h, nq, d) over k, v (b, hk, n, dv).
+
+    `tree_mask` / `causal` verify drafts on the dense cache with
+    tree_attn_decode_paged's meaning (minus the window): the last nq keys of
+    the sequence are the drafts' own tokens, tree_mask[i, t] (bool (b, nq, nq)
+    or (nq, nq), diagonal set, nq <= 64, n >= nq) lets draft i attend key
+    n - nq + t, every draft attends the whole prefix, and `causal=True` is the
+    lower-triangular mask; the two exclude each other.  Either runs the grouped
+    MFMA kernel (csrc/decode_grouped.hip), which streams K/V once for all
+    (group-mate, draft) rows of a kv head; `grouped=True` takes it for a plain
+    call, `grouped=False` with a mask is a ValueError (the row kernel has no
+    key limit per row), and a call with none of the three runs the row kernel
+    as before.
+
+    With `shard_kv_seq=True` the mask goes to the rank that holds the last
+    chunk of `k.chunk(world)`, which must hold at least nq keys (ValueError on
+    every rank otherwise); the other ranks run unmasked.  With
+    `shard_kv_seq=False` the caller passes the mask only on the rank that
+    holds the tail.
+    """
     assert (k is None) == (v is None)
     dtype = q.dtype
     b, h, nq, d = q.shape
+    name = "tree_attn_decode"
 
     # capture the value dim from the FULL v before chunking: a rank whose
     # shard is empty must still pack a (b,h,1,1+dv)-shaped all-reduce buffer,
     # and dv may differ from q's head dim d
     dim_v = v.shape[-1] if v is not None else d
 
+    masked_here = tree_mask is not None or causal
     if shard_kv_seq:
         assert k is not None
         rank, world = get_rank(), get_world_size()
+        if masked_here:
+            masked_here = rank == _tail_shard(k.shape[-2], world, nq, name)
         ks = k.chunk(world, dim=-2)
         vs = v.chunk(world, dim=-2)
         k, v = (ks[rank], vs[rank]) if rank < len(ks) else (None, None)
 
+    use_grouped, vis = _dense_visibility(
+        name, tree_mask, grouped, causal, b, nq,
+        None if k is None else k.shape[-2], q.device, masked_here)
+
     if v is not None:
-        local_out, lse = _local_decode_partial(q, k, v, use_hip_kernel)
+        local_out, lse = _local_decode_partial(q, k, v, use_hip_kernel, vis, use_grouped)
     else:
         # seq shorter than world: this rank holds nothing
         local_out = q.new_zeros((b, h, nq, dim_v), dtype=torch.float32)
@@ -121,6 +205,9 @@ def tree_attn_decode_fp8(
     q: Tensor,
     k8: Tensor, v8: Tensor, ks: Tensor, vs: Tensor,
     eps: float = 1e-8,
+    causal: bool = False,
+    tree_mask: Tensor | None = None,
+    grouped: bool | None = None,
 ) -> Tensor:
     """Tree-attention decode over an FP8-quantized LOCAL KV-cache shard.
 
@@ -130,13 +217,24 @@ def tree_attn_decode_fp8(
     identical to tree_attn_decode (2 collective rounds).  Each rank passes
     its own pre-quantized shard (there is no in-function sharding: a serving
     cache lives pre-sharded next to its rank).
+
+    `causal`, `tree_mask` and `grouped` are tree_attn_decode's: the last nq
+    keys of the shard are the drafts' own tokens, so only the rank that holds
+    the tail of the sequence passes a mask.
     """
     dtype = q.dtype
-    d = q.shape[-1]
+    b, _, nq, d = q.shape
+    use_grouped, vis = _dense_visibility("tree_attn_decode_fp8", tree_mask, grouped,
+                                         causal, b, nq, k8.shape[-2], q.device)
     if q.is_cuda:
         from .ops import hip_ext
-        outs, lses = hip_ext.require().decode_partial_fp8(
-            q.to(torch.bfloat16).contiguous(), k8, v8, ks, vs, d ** -0.5)
+        if use_grouped:
+            outs, lses = hip_ext.require().decode_partial_grouped(
+                q.to(torch.bfloat16).contiguous(), k8, v8, ks, vs, d ** -0.5, 0,
+                None if vis is None else _tree_bits(vis))
+        else:
+            outs, lses = hip_ext.require().decode_partial_fp8(
+                q.to(torch.bfloat16).contiguous(), k8, v8, ks, vs, d ** -0.5)
         local_out, lse = hip_ext.require().decode_merge(outs, lses)
     else:
         # CPU fallback: dequantize the cache and run the eager partial (the
@@ -146,7 +244,7 @@ def tree_attn_decode_fp8(
               * torch.exp2(ks.float() - 127.0).unsqueeze(-1))
         vd = (v8.view(torch.float8_e4m3fn).float()
               * torch.exp2(vs.float() - 127.0).unsqueeze(-1))
-        local_out, lse = _local_decode_partial(q, kd, vd)
+        local_out, lse = _local_decode_partial(q, kd, vd, vis=vis)
     return _merge_across_ranks(local_out, lse, dtype, eps)
 
 
@@ -173,19 +271,31 @@ def _tree_visibility(tree_mask, grouped, causal: bool, window, cache, b: int,
     name = "tree_attn_decode_paged"
     if tree_mask is None and not grouped:
         return False, None
-    if tree_mask is not None and grouped is False:
-        raise ValueError(f"{name}: tree_mask needs the grouped kernel (grouped=False given)")
-    if tree_mask is not None and causal:
-        raise ValueError(f"{name}: tree_mask and causal=True exclude each other "
-                         "(a chain is the lower-triangular mask)")
+    _check_mask_args(name, tree_mask, grouped, causal)
     if tree_mask is not None and (window is not None or any(cache.host_starts)):
         raise ValueError(f"{name}: a tree mask serves neither a window nor a cache "
                          "with released pages (a draft's position is its depth)")
     if tree_mask is None and not causal:
         return True, None
+    return True, _draft_visibility(name, tree_mask, cache.host_lens, b, nq, device)
+
+
+def _check_mask_args(name: str, tree_mask, grouped, causal: bool) -> None:
+    """What a tree_mask excludes, for the paged and the dense entry points."""
+    if tree_mask is not None and grouped is False:
+        raise ValueError(f"{name}: tree_mask needs the grouped kernel (grouped=False given)")
+    if tree_mask is not None and causal:
+        raise ValueError(f"{name}: tree_mask and causal=True exclude each other "
+                         "(a chain is the lower-triangular mask)")
+
+
+def _draft_visibility(name: str, tree_mask, lens, b: int, nq: int, device) -> Tensor:
+    """Host checks of a masked grouped call (no device read beyond the
+    mask's diagonal) -> (b, nq, nq) bool; tree_mask None is the chain.
+    `lens`: the sequences' cached lengths."""
     if nq > 64:
         raise ValueError(f"{name}: a tree mask covers at most 64 drafts (nq = {nq})")
-    if any(0 < n < nq for n in cache.host_lens):
+    if any(0 < n < nq for n in lens):
         raise ValueError(f"{name}: a masked sequence holds 0 or at least nq = {nq} tokens")
     if tree_mask is None:
         vis = torch.ones(nq, nq, dtype=torch.bool, device=device).tril()
@@ -197,7 +307,7 @@ def _tree_visibility(tree_mask, grouped, causal: bool, window, cache, b: int,
         raise ValueError(f"{name}: tree_mask must be (nq, nq) or (b, nq, nq)")
     if not bool(vis.diagonal(dim1=-2, dim2=-1).all()):
         raise ValueError(f"{name}: every draft attends itself (tree_mask diagonal)")
-    return True, vis
+    return vis
 
 
 def _tree_bits(vis: Tensor) -> Tensor:

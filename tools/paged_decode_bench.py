@@ -26,8 +26,14 @@ head, bf16 and fp8, page size 64, shuffled table, alternating in the same
 rounds, and returns; `vs_row` is grouped / row.  With `--window` both kernels
 take `window=W` over the `--kv-len` cached keys, one group per W.
 
+`--dense-grouped NQ [NQ ...]` does the same on the DENSE cache: the row kernel
+(decode_partial / decode_partial_fp8) against csrc/decode_grouped.hip with at
+most 1, 2 and 4 row tiles per workgroup (RING_ATTN_GROUPED_TILES, as far as the
+shape has that many) and as the launcher picks them; `vs_row` is grouped / row.
+
     python tools/paged_decode_bench.py [--kv-len 131072] [--rounds 7] [--out F]
         [--window 1024 4096 32768] [--only-window] [--grouped 1 4 16]
+        [--dense-grouped 1 4 16]
 """
 
 from __future__ import annotations
@@ -76,17 +82,30 @@ def dense_step(q, k, v, fp8):
     return step
 
 
+def dense_grouped_step(q, k, v, fp8):
+    """The grouped MFMA kernel on the dense cache (partial + merge)."""
+    ext = hip_ext.require()
+    c = quantize_kv_cache(k, v) if fp8 else (k, v, None, None)
+    scale = q.shape[-1] ** -0.5
+    return lambda: ext.decode_merge(*ext.decode_partial_grouped(q, *c, scale))
+
+
+def with_env(fn, name, value):
+    """Same step with one of the bindings' A/B environment switches set."""
+    def step():
+        os.environ[name] = value
+        try:
+            return fn()
+        finally:
+            del os.environ[name]
+    return step
+
+
 def ordered(fn, order):
     """Same step with the workgroup order forced: "row" = the dense kernels'
     (row block fast, kv chunk slow), "chunk" = kv chunk fast.  Unforced, the
     binding picks row for b == 1 and chunk for b > 1."""
-    def step():
-        os.environ["RING_ATTN_PAGED_ORDER"] = order
-        try:
-            return fn()
-        finally:
-            del os.environ["RING_ATTN_PAGED_ORDER"]
-    return step
+    return with_env(fn, "RING_ATTN_PAGED_ORDER", order)
 
 
 def run_group(name, steps, args, results, note="", base_of=None, ratio="vs_dense"):
@@ -125,6 +144,10 @@ def main():
     ap.add_argument("--grouped", type=int, nargs="*", default=[],
                     help="query tokens per head: time grouped=True against the "
                          "row kernel (ps 64, shuffled) and nothing else")
+    ap.add_argument("--dense-grouped", type=int, nargs="*", default=[],
+                    help="query tokens per head: time the grouped kernel on the DENSE "
+                         "cache (at most 1, 2, 4 tiles per workgroup and its own pick) "
+                         "against the dense row kernel and nothing else")
     ap.add_argument("--out", default=None, help="also write the records here (JSON)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "paged_decode_bench needs a GPU"
@@ -177,6 +200,27 @@ def main():
                           + ("" if w is None else f" window={w}"),
                           steps, args, results, base_of=lambda label: "row", ratio="vs_row")
     if args.grouped:
+        return write(args, results)
+
+    # ---- dense cache: grouped MFMA kernel vs the dense row kernel -----------
+    for nq in args.dense_grouped:
+        qn = torch.randn(1, h, nq, d, device=dev, dtype=bf)
+        tiles = -(-(h // hk) * nq // 32)
+        caps = [c for c in (1, 2, 4) if c == 1 or c // 2 < min(tiles, 4 if d == 64 else 2)]
+        for fp8 in (False, True):
+            steps = {"row": dense_step(qn, k, v, fp8)}
+            fn = dense_grouped_step(qn, k, v, fp8)
+            for cap in caps + [None]:
+                steps["grouped" if cap is None else f"grouped tiles<={cap}"] = (
+                    fn if cap is None else with_env(fn, "RING_ATTN_GROUPED_TILES", str(cap)))
+            ref = steps["row"]()[0]
+            for label, fn in steps.items():
+                err = (fn()[0] - ref).abs().max().item()
+                assert err < 5e-3, (nq, fp8, label, err)
+            run_group(f"dense {'fp8' if fp8 else 'bf16'} b=1 kv={n} {h}q/{hk}kv nq={nq}",
+                      steps, args, results, base_of=lambda label: "row", ratio="vs_row",
+                      note=f"{tiles} row tile(s) per kv head")
+    if args.dense_grouped:
         return write(args, results)
 
     # ---- sliding window: kv-len cached, window w, vs w + 1 keys cached -----
