@@ -493,10 +493,47 @@ struct PagedPrefillParams {
     long win;
     float scale;
     int kv_split;           // grid.z shares of each workgroup's own tile range
+    // ---- work-unit launches only (launch_attn_fwd_paged_units): q and out
+    // are packed (total, H, D), lse is (H, total) and t holds `total`; the
+    // partials are per slot: o (slots, H, D, 256), m and l (slots, H, 256)
+    const int* units;       // int32 (n_units, PAGED_UNIT_INTS), see below
+    int n_units, n_slots;
+};
+
+// One work unit of the varlen paged prefill: one 256-row q tile of one
+// sequence and share z of `count` of that tile's own kv tile range.
+constexpr int PAGED_UNIT_INTS = 8;
+enum PagedUnitField {
+    PU_SEQ = 0,     // sequence id
+    PU_QTILE = 1,   // q tile index inside the sequence
+    PU_QROW0 = 2,   // packed row of the tile's first q row
+    PU_Z = 3,       // share index, 0 <= z < count
+    PU_COUNT = 4,   // shares of this tile; 1 = the unit writes out / lse itself
+    PU_SLOT0 = 5,   // count > 1: share z writes partial slot slot0 + z
 };
 
 void launch_attn_fwd_paged(const PagedPrefillParams& p, int head_dim, bool fp8,
                            hipStream_t stream);
+// grid (n_units, H): every workgroup takes its geometry from its unit row
+void launch_attn_fwd_paged_units(const PagedPrefillParams& p, int head_dim, bool fp8,
+                                 hipStream_t stream);
+
+// Merge of the work units' shares: one workgroup per (tile with count > 1,
+// head), one thread per q row, any count.
+struct PagedMergeUnitsParams {
+    const float* o_part;    // fp32 (slots, H, D, 256) unnormalized shares
+    const float* m_part;    // fp32 (slots, H, 256), natural log; MASK = empty
+    const float* l_part;    // fp32 (slots, H, 256)
+    const int* tiles;       // int32 (n_tiles, 4): slot0, count, first packed
+                            // row, valid rows
+    void* out;              // bf16 (total, H, D)
+    float* lse;             // fp32 (H, total)
+    int n_tiles, n_slots, h;
+    long total;
+};
+
+void launch_attn_fwd_merge_units(const PagedMergeUnitsParams& p, int head_dim,
+                                 hipStream_t stream);
 
 // Fp8FwdCore is all a launch with the standard mask reads, and all that the
 // instantiations with the constant mask take as their kernel argument (the

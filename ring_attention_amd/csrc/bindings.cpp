@@ -904,6 +904,122 @@ void attn_fwd_paged(
     TORCH_CHECK(hipGetLastError() == hipSuccess, "paged prefill launch failed");
 }
 
+void attn_fwd_paged_units(
+    at::Tensor q, at::Tensor k_pages, at::Tensor v_pages,
+    std::optional<at::Tensor> k_scales, std::optional<at::Tensor> v_scales,
+    at::Tensor block_table, at::Tensor seq_lens, at::Tensor q_lens,
+    at::Tensor units, at::Tensor out, at::Tensor lse,
+    std::optional<at::Tensor> o_part, std::optional<at::Tensor> m_part,
+    std::optional<at::Tensor> l_part,
+    double scale, bool causal, int64_t win, bool has_win) {
+    // q, out bf16 packed (total,H,D); lse fp32 (H,total); pool operands and
+    // q_lens as attn_fwd_paged; units int32 (U, PAGED_UNIT_INTS).  Units with
+    // count > 1 write slot slot0 + z of o_part (slots,H,D,256) and m_part,
+    // l_part (slots,H,256) for attn_fwd_merge_units; without partials every
+    // unit must have count 1 (the kernel then stores no share).
+    CHECK_BF16_CONTIG(q);
+    TORCH_CHECK(q.dim() == 3, "q must be packed (total,H,D)");
+    const int64_t total = q.size(0), H = q.size(1), D = q.size(2);
+    const int64_t B = seq_lens.dim() == 1 ? seq_lens.size(0) : -1;
+    bool fp8 = false;
+    const int shift = check_paged_pool(q, k_pages, v_pages, k_scales, v_scales,
+                                       block_table, seq_lens, B, D, &fp8);
+    const int64_t HK = k_pages.size(1);
+    TORCH_CHECK(H % HK == 0, "q heads must be a multiple of kv heads");
+    TORCH_CHECK(q_lens.scalar_type() == at::kInt && q_lens.is_contiguous()
+                && q_lens.dim() == 1 && q_lens.size(0) == B
+                && q_lens.device() == q.device(),
+                "q_lens must be contiguous int32 (B,) on the same device");
+    TORCH_CHECK(units.scalar_type() == at::kInt && units.is_contiguous()
+                && units.dim() == 2 && units.size(1) == PAGED_UNIT_INTS
+                && units.device() == q.device(),
+                "units must be contiguous int32 (U, ", PAGED_UNIT_INTS, ") on the same device");
+    const int64_t U = units.size(0);
+    TORCH_CHECK(H <= 65535, "H must fit grid.y");
+    TORCH_CHECK(U < (int64_t(1) << 31) && total < (int64_t(1) << 31), "launch too large");
+    TORCH_CHECK(!has_win || win >= 0, "window must be >= 0");
+    CHECK_BF16_CONTIG(out); CHECK_F32_CONTIG(lse);
+    TORCH_CHECK(out.sizes() == q.sizes() && lse.numel() == H * total
+                && out.device() == q.device() && lse.device() == q.device(),
+                "out must be (total,H,D) and lse (H,total)");
+    PagedPrefillParams p{};
+    if (o_part || m_part || l_part) {
+        TORCH_CHECK(o_part && m_part && l_part, "partials come as o, m and l together");
+        CHECK_F32_CONTIG((*o_part)); CHECK_F32_CONTIG((*m_part)); CHECK_F32_CONTIG((*l_part));
+        const int64_t slots = m_part->numel() / (H * ROWS_WG);
+        TORCH_CHECK(m_part->numel() == slots * H * ROWS_WG
+                    && l_part->numel() == slots * H * ROWS_WG
+                    && o_part->numel() == slots * H * D * ROWS_WG
+                    && slots < (int64_t(1) << 31)
+                    && o_part->device() == q.device() && m_part->device() == q.device()
+                    && l_part->device() == q.device(),
+                    "partials must be (slots,H,D,256) and (slots,H,256)");
+        p.o_part = o_part->data_ptr<float>();
+        p.m_part = m_part->data_ptr<float>();
+        p.l_part = l_part->data_ptr<float>();
+        p.n_slots = (int)slots;
+    }
+    if (U * H * total == 0) return;
+    p.q = q.data_ptr();
+    p.k_pages = k_pages.data_ptr(); p.v_pages = v_pages.data_ptr();
+    if (fp8) { p.kscale = k_scales->data_ptr(); p.vscale = v_scales->data_ptr(); }
+    p.block_table = block_table.data_ptr<int>();
+    p.seq_lens = seq_lens.data_ptr<int>();
+    p.q_lens = q_lens.data_ptr<int>();
+    p.units = units.data_ptr<int>();
+    p.out = out.data_ptr();
+    p.lse = lse.data_ptr<float>();
+    p.b = (int)B; p.h = (int)H; p.hk = (int)HK; p.t = (int)total;
+    p.page_shift = shift;
+    p.max_pages = (int)block_table.size(1);
+    p.num_pages = (int)k_pages.size(0);
+    p.causal = causal ? 1 : 0; p.has_win = has_win ? 1 : 0; p.win = win;
+    p.scale = (float)scale;
+    p.kv_split = 1;
+    p.n_units = (int)U;
+    launch_attn_fwd_paged_units(p, (int)D, fp8, at::hip::getCurrentHIPStream());
+    TORCH_CHECK(hipGetLastError() == hipSuccess, "paged prefill units launch failed");
+}
+
+void attn_fwd_merge_units(
+    at::Tensor o_part, at::Tensor m_part, at::Tensor l_part, at::Tensor tiles,
+    at::Tensor out, at::Tensor lse) {
+    // o_part fp32 (slots,H,D,256), m_part / l_part (slots,H,256); tiles int32
+    // (M,4) [slot0, count, first packed row, valid rows]; out bf16
+    // (total,H,D), lse fp32 (H,total)
+    CHECK_F32_CONTIG(o_part); CHECK_F32_CONTIG(m_part); CHECK_F32_CONTIG(l_part);
+    CHECK_BF16_CONTIG(out); CHECK_F32_CONTIG(lse);
+    TORCH_CHECK(out.dim() == 3, "out must be packed (total,H,D)");
+    const int64_t total = out.size(0), H = out.size(1), D = out.size(2);
+    TORCH_CHECK(D == 64 || D == 128, "head dim must be 64 or 128");
+    TORCH_CHECK(H >= 1 && H <= 65535, "H must fit grid.y");
+    const int64_t slots = m_part.numel() / (H * ROWS_WG);
+    TORCH_CHECK(m_part.numel() == slots * H * ROWS_WG && l_part.numel() == slots * H * ROWS_WG
+                && o_part.numel() == slots * H * D * ROWS_WG && slots < (int64_t(1) << 31),
+                "partials must be (slots,H,D,256) and (slots,H,256)");
+    TORCH_CHECK(lse.numel() == H * total && total < (int64_t(1) << 31),
+                "lse must be (H,total)");
+    TORCH_CHECK(tiles.scalar_type() == at::kInt && tiles.is_contiguous()
+                && tiles.dim() == 2 && tiles.size(1) == 4,
+                "tiles must be contiguous int32 (M,4)");
+    for (const at::Tensor* t : {&o_part, &m_part, &l_part, &tiles, &lse})
+        TORCH_CHECK(t->device() == out.device(), "all operands must be on one device");
+    const int64_t M = tiles.size(0);
+    TORCH_CHECK(M < (int64_t(1) << 31), "too many tiles");
+    if (M * total == 0) return;
+    PagedMergeUnitsParams p{};
+    p.o_part = o_part.data_ptr<float>();
+    p.m_part = m_part.data_ptr<float>();
+    p.l_part = l_part.data_ptr<float>();
+    p.tiles = tiles.data_ptr<int>();
+    p.out = out.data_ptr();
+    p.lse = lse.data_ptr<float>();
+    p.n_tiles = (int)M; p.n_slots = (int)slots; p.h = (int)H;
+    p.total = total;
+    launch_attn_fwd_merge_units(p, (int)D, at::hip::getCurrentHIPStream());
+    TORCH_CHECK(hipGetLastError() == hipSuccess, "paged merge units launch failed");
+}
+
 at::Tensor attn_delta(at::Tensor dout, at::Tensor out) {
     // dout, out (B,N,H,D) bf16 -> delta fp32 (B,H,N) = rowsum(dout*out)
     CHECK_BF16_CONTIG(dout); CHECK_BF16_CONTIG(out);
@@ -1005,6 +1121,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::arg("o_part"), py::arg("m_part"), py::arg("l_part"),
             py::arg("scale"), py::arg("causal"), py::arg("win"),
             py::arg("has_win"), py::arg("kv_split"));
+    mod.def("attn_fwd_paged_units", &ring_attn::attn_fwd_paged_units,
+            "CDNA4 varlen paged prefill: packed q, one workgroup per work unit",
+            py::arg("q"), py::arg("k_pages"), py::arg("v_pages"),
+            py::arg("k_scales"), py::arg("v_scales"), py::arg("block_table"),
+            py::arg("seq_lens"), py::arg("q_lens"), py::arg("units"),
+            py::arg("out"), py::arg("lse"),
+            py::arg("o_part"), py::arg("m_part"), py::arg("l_part"),
+            py::arg("scale"), py::arg("causal"), py::arg("win"), py::arg("has_win"));
+    mod.def("attn_fwd_merge_units", &ring_attn::attn_fwd_merge_units,
+            "merge the work units' shares into packed out / lse",
+            py::arg("o_part"), py::arg("m_part"), py::arg("l_part"),
+            py::arg("tiles"), py::arg("out"), py::arg("lse"));
     // host access to attn_mask.h, the kernels' own mask geometry (no GPU
     // needed): the descriptor builder takes its shapes and bounds from here,
     // and the CPU tests hold it to a brute-force mask

@@ -182,3 +182,192 @@ def paged_prefill_attn(
     if d != kd:
         out = out[..., :d]
     return (out, lse) if return_lse else out
+
+
+# ---------------------------------------------------------------------------
+# varlen form: packed queries, one workgroup per work unit
+# ---------------------------------------------------------------------------
+_UNIT_INTS = 8              # csrc/attn_common.h PAGED_UNIT_INTS
+_UNIT_TARGET_WGS = 2 * 256  # planner: workgroups aimed at, over all heads
+_UNIT_MIN_TILES = 4         # planner: smallest share worth a partial + merge
+
+
+def plan_units(seq_lens, q_lens, h: int, kernel_dim: int, causal: bool = True,
+               window: int | None = None, unit_tiles: int = 0,
+               target_workgroups: int | None = None,
+               min_tiles: int | None = None):
+    """Work units of one varlen call, on the host (nothing is read back).
+
+    A unit is one 256-row q tile of one sequence and share z of `count` of
+    that tile's own kv tile range.  With W_t the tile count of q tile t (the
+    kernels' own `Mask.kv_tile_range`, through the extension) the shares hold
+    at most per = max(min_tiles, ceil(sum(W) * h / target_workgroups)) kv
+    tiles (`unit_tiles` > 0 replaces per), count_t = max(1, ceil(W_t / per)),
+    and the kernel cuts the range itself with `split_share`.  Units come
+    longest share first.  There are at most (live q tiles) +
+    target_workgroups / h of them.
+
+    `target_workgroups` / `min_tiles` default to the module's measured
+    _UNIT_TARGET_WGS / _UNIT_MIN_TILES (docs/KERNELS.md section 3b).
+
+    Returns (units, merges, slots): int rows [seq, qtile, first packed row, z,
+    count, slot0, 0, 0]; for every tile with count > 1 a row [slot0, count,
+    first packed row, valid rows]; and the number of partial slots (share z
+    of a tile writes slot slot0 + z).
+    """
+    from .ops import hip_ext
+    ext = hip_ext.require()
+    if target_workgroups is None:
+        target_workgroups = _UNIT_TARGET_WGS
+    if min_tiles is None:
+        min_tiles = _UNIT_MIN_TILES
+    width = ext.mask_tile_shapes(kernel_dim)["kvblk"]
+    has_win, win = window is not None, 0 if window is None else int(window)
+    tiles, row0 = [], 0
+    for i, (n, ql) in enumerate(zip(seq_lens, q_lens)):
+        mask = ext.Mask(bool(causal), n - ql, 1, has_win, win)
+        for x in range(-(-ql // _ROWS_WG)):
+            rows = min(_ROWS_WG, ql - x * _ROWS_WG)
+            lo, hi = mask.kv_tile_range(x * _ROWS_WG, x * _ROWS_WG + rows - 1, n, width)
+            tiles.append((i, x, row0 + x * _ROWS_WG, rows, hi - lo))
+        row0 += ql
+    if unit_tiles > 0:
+        per = int(unit_tiles)
+    else:
+        work = sum(t[4] for t in tiles) * h
+        per = max(int(min_tiles), -(-work // max(1, int(target_workgroups))))
+    keyed, merges, slots = [], [], 0
+    for i, x, first, rows, w in tiles:
+        count = max(1, -(-w // per))
+        share = -(-w // count)                  # split_share's own cut
+        slot0 = slots if count > 1 else 0
+        if count > 1:
+            merges.append([slot0, count, first, rows])
+            slots += count
+        for z in range(count):
+            keyed.append((max(0, min(share, w - z * share)),
+                          [i, x, first, z, count, slot0, 0, 0]))
+    keyed.sort(key=lambda u: -u[0])             # stable: longest share first
+    return [u for _, u in keyed], merges, slots
+
+
+@torch.no_grad()
+def paged_prefill_attn_varlen(
+    q: Tensor,
+    cache,
+    q_lens,
+    causal: bool = True,
+    window: int | None = None,
+    return_lse: bool = False,
+    use_hip_kernel: bool | None = None,
+    unit_tiles: int = 0,
+):
+    """`paged_prefill_attn` for packed queries, balanced over ragged batches.
+
+    q (total, h, d) holds the chunks back to back: sequence i's rows are
+    [cu[i], cu[i] + q_lens[i]) with cu the running sum of `q_lens` (a host
+    list or int tensor, 0 <= q_lens[i] <= seq_len[i], sum == total).
+    Positions, `causal`, `window`, released pages, the qh % hk pairing, small
+    head dims and fp8 pools are `paged_prefill_attn`'s.
+
+    Returns out bf16 (total, h, d); with `return_lse` also lse fp32
+    (h, total), natural log.  A row with no attendable key returns out == 0
+    and a finite lse <= -1e30.
+
+    On CUDA the launch is a flat list of work units (`plan_units`): every
+    workgroup of `attn_fwd_paged_kernel<.., UNITS>` takes one q tile of one
+    sequence and one share of that tile's own kv range, so a long sequence is
+    split as finely as it needs while a short one is not split at all, and
+    `attn_fwd_merge_units` combines the shares.  `unit_tiles=0` lets the
+    planner size the shares; a positive value forces "at most this many kv
+    tiles per unit" (tests, A/B runs; a huge value = one unit per q tile).
+    The HIP kernels are the only GPU path (`hip_ext.require()`); on CPU, or
+    with use_hip_kernel=False, the eager fp32 fallback runs on the padded
+    batch.
+    """
+    name = "paged_prefill_attn_varlen"
+    if q.requires_grad:
+        raise RuntimeError(
+            f"{name} is a serving path without a backward pass: "
+            "q must not require grad (detach it)")
+    if q.dim() != 3:
+        raise ValueError(f"{name}: q must be packed (total, h, d)")
+    total, h, d = q.shape
+    b = cache.max_seqs
+    if d != cache.dim_head:
+        raise ValueError(f"{name}: q head dim {d} != cache.dim_head {cache.dim_head}")
+    if h % cache.kv_heads != 0:
+        raise ValueError(f"{name}: {h} q heads are not a multiple of "
+                         f"{cache.kv_heads} kv heads")
+    if window is not None and window < 0:
+        raise ValueError(f"{name}: window must be >= 0")
+    if unit_tiles < 0:
+        raise ValueError(f"{name}: unit_tiles must be >= 0")
+    if isinstance(q_lens, Tensor):
+        q_lens = q_lens.tolist()
+    lens = [int(x) for x in q_lens]
+    seq_lens = cache.host_lens
+    if len(lens) != b:
+        raise ValueError(f"{name}: q_lens has {len(lens)} entries, the cache "
+                         f"holds {b} sequences")
+    for i, (ql, n) in enumerate(zip(lens, seq_lens)):
+        if not 0 <= ql <= n:
+            raise ValueError(f"{name}: q_lens[{i}] = {ql} must lie in [0, seq_len = {n}] "
+                             f"— append the chunk to the cache before attending")
+    if sum(lens) != total:
+        raise ValueError(f"{name}: q holds {total} rows, q_lens sum to {sum(lens)}")
+    if any(cache.host_starts):
+        cache.check_released(
+            name,
+            None if window is None else
+            [max(0, n - ql - int(window)) if ql > 0 else None
+             for n, ql in zip(seq_lens, lens)])
+
+    if not (q.is_cuda and use_hip_kernel is not False):
+        # pad to (b, T, h, d), run the eager path, unpack
+        t = max(lens, default=0)
+        qp = q.new_zeros(b, t, h, d)
+        row0 = 0
+        for i, ql in enumerate(lens):
+            qp[i, :ql] = q[row0:row0 + ql]
+            row0 += ql
+        out_p, lse_p = _eager(qp, cache, lens, causal, window)
+        out = torch.cat([out_p[i, :ql] for i, ql in enumerate(lens)])
+        lse = torch.cat([lse_p[i, :, :ql] for i, ql in enumerate(lens)], dim=1)
+        return (out, lse) if return_lse else out
+
+    from .ops import hip_ext
+    ext = hip_ext.require()           # no eager fallback on GPU
+    kd = cache.kernel_dim
+    qb = (F.pad(q, (0, kd - d)) if d != kd else q).to(torch.bfloat16).contiguous()
+    out = torch.empty_like(qb)
+    lse = torch.empty(h, total, device=q.device, dtype=torch.float32)
+    if total * h == 0:
+        return (out[..., :d], lse) if return_lse else out[..., :d]
+    units, merges, slots = plan_units(seq_lens, lens, h, kd, causal, window, unit_tiles)
+    # q_lens (padded to a whole unit row), the unit table and the merge table
+    # in one host tensor: one H2D copy per call
+    head = -(-b // _UNIT_INTS) * _UNIT_INTS
+    flat = lens + [0] * (head - b)
+    for row in units:
+        flat.extend(row)
+    for row in merges:
+        flat.extend(row)
+    dev = torch.tensor(flat, dtype=torch.int32).to(q.device)
+    q_lens_dev = dev[:b]
+    units_dev = dev[head:head + len(units) * _UNIT_INTS].view(len(units), _UNIT_INTS)
+    merges_dev = dev[head + len(units) * _UNIT_INTS:].view(len(merges), 4)
+    parts = (None, None, None)
+    if slots:
+        parts = (torch.empty(slots, h, kd, _ROWS_WG, device=q.device, dtype=torch.float32),
+                 torch.empty(slots, h, _ROWS_WG, device=q.device, dtype=torch.float32),
+                 torch.empty(slots, h, _ROWS_WG, device=q.device, dtype=torch.float32))
+    ext.attn_fwd_paged_units(
+        qb, cache.k_pages, cache.v_pages, cache.k_scales, cache.v_scales,
+        cache.block_table, cache.seq_lens, q_lens_dev, units_dev, out, lse, *parts,
+        d ** -0.5, causal, 0 if window is None else int(window), window is not None)
+    if slots:
+        ext.attn_fwd_merge_units(*parts, merges_dev, out, lse)
+    if d != kd:
+        out = out[..., :d]
+    return (out, lse) if return_lse else out

@@ -9,15 +9,20 @@ Times, forward only,
   paged ...      : paged_prefill_attn on the PagedKVCache holding the tokens,
                    for page_size in {16, 64, 256} x identity / shuffled tables,
                    with the automatic split (and split=1 where that differs)
+  varlen ...     : paged_prefill_attn_varlen on the same cache and the packed
+                   queries (work units sized by the planner), shuffled tables
 on: a full causal prefill of one prompt, a chunk over a long cached context,
 and a ragged b = 8 batch of chunks over contexts 1k .. 128k (the dense path
 serves that one sequence at a time).
+
+A last group sweeps the planner's two numbers (target_workgroups, min_tiles)
+on the ragged batch.
 
 All steps of a group ALTERNATE inside every round (the box is shared); the
 median over the rounds is reported with min / max; each measurement is
 `--iters` calls between two device events after a warm-up.
 
-    python tools/paged_prefill_bench.py [--rounds 5] [--out F]
+    python tools/paged_prefill_bench.py [--rounds 5] [--dims 64] [--out F]
 """
 
 from __future__ import annotations
@@ -32,7 +37,9 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from ring_attention_amd import PagedKVCache, paged_prefill_attn     # noqa: E402
+from ring_attention_amd import (PagedKVCache, paged_prefill_attn,   # noqa: E402
+                                paged_prefill_attn_varlen)
+from ring_attention_amd import paged_prefill as pp                  # noqa: E402
 from ring_attention_amd.ops import hip_ext                          # noqa: E402
 from ring_attention_amd.ops.ring_flash_hip import flash_attn_offset  # noqa: E402
 from ring_attention_amd.paged_prefill import auto_kv_split          # noqa: E402
@@ -88,12 +95,12 @@ def dense_split_step(q, k, v, q_offset, split):
     return step
 
 
-def run_group(name, steps, args, results, note=""):
+def run_group(name, steps, args, results, note="", base="dense"):
     samples = {label: [] for label in steps}
     for _ in range(args.rounds):
         for label, fn in steps.items():
             samples[label].append(time_us(fn, args.iters, args.warmup))
-    base = statistics.median(samples["dense"])
+    base = statistics.median(samples[base])
     for label, xs in samples.items():
         med = statistics.median(xs)
         rec = {"group": name, "config": label, "median_us": round(med, 1),
@@ -111,6 +118,8 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--page-sizes", type=int, nargs="+", default=[16, 64, 256])
+    ap.add_argument("--dims", type=int, nargs="+", default=[64, 128],
+                    help="head dims of the one-sequence shapes (fp8 runs at 64)")
     ap.add_argument("--out", default=None, help="also write the records here (JSON)")
     args = ap.parse_args()
     assert args.rounds >= 5, "report a median of at least 5 rounds"
@@ -148,13 +157,16 @@ def main():
                 if split > 1 and kind == "shuffled":
                     steps[f"paged ps={ps} {kind} split=1"] = (
                         lambda c=cache: paged_prefill_attn(q, c, [t], causal=True, kv_split=1))
+                if kind == "shuffled":
+                    steps[f"varlen ps={ps} {kind}"] = (
+                        lambda c=cache: paged_prefill_attn_varlen(q[0], c, [t], causal=True)[None])
         for label, fn in steps.items():       # same result before anything is timed
             err = (fn().float() - ref).abs().max().item()
             assert err < 2e-2, (label, err)
         tag = f"{'fp8' if fp8 else 'bf16'} d={d} T={t} over kv={n}"
         run_group(tag, steps, args, results, note=f"auto kv_split={split}")
 
-    for d, fp8 in ((64, False), (128, False), (64, True)):
+    for d, fp8 in [(d, False) for d in args.dims] + [(64, True)] * (64 in args.dims):
         one_sequence(8192, 8192, d, fp8)        # full causal prefill of one prompt
         one_sequence(2048, 32768, d, fp8)       # a chunk over a cached context
 
@@ -183,13 +195,34 @@ def main():
             ref = torch.cat(dense_loop()).float()
         steps[f"paged ps={ps} shuffled"] = (
             lambda c=cache: paged_prefill_attn(q, c, [t] * b, causal=True))
-        err = (steps[f"paged ps={ps} shuffled"]().float() - ref).abs().max().item()
-        assert err < 2e-2, (ps, err)
+        steps[f"varlen ps={ps} shuffled"] = (
+            lambda c=cache: paged_prefill_attn_varlen(q.view(b * t, h, d), c, [t] * b,
+                                                      causal=True).view(b, t, h, d))
+        for label in (f"paged ps={ps} shuffled", f"varlen ps={ps} shuffled"):
+            err = (steps[label]().float() - ref).abs().max().item()
+            assert err < 2e-2, (label, err)
     del k, v
     run_group(f"bf16 d={d} ragged b={b} T={t} over kv={lens[0]}..{lens[-1]}",
               steps, args, results,
               note="dense runs one sequence per launch (8 launches); "
                    f"paged auto kv_split={auto_kv_split(t, b, h, n, d)}")
+
+    # ---- the planner's two numbers on the ragged batch (last cache)
+    def with_planner(target, min_tiles):
+        def step():
+            saved = pp._UNIT_TARGET_WGS, pp._UNIT_MIN_TILES
+            pp._UNIT_TARGET_WGS, pp._UNIT_MIN_TILES = target, min_tiles
+            try:
+                return paged_prefill_attn_varlen(q.view(b * t, h, d), cache, [t] * b, causal=True)
+            finally:
+                pp._UNIT_TARGET_WGS, pp._UNIT_MIN_TILES = saved
+        return step
+    default = (pp._UNIT_TARGET_WGS, pp._UNIT_MIN_TILES)
+    sweep = {f"target={tg} min_tiles={mt}": with_planner(tg, mt)
+             for tg in (256, 512, 1024, 2048) for mt in (2, 4, 8)}
+    run_group(f"planner sweep, ragged b={b} ps={cache.page_size}", sweep, args, results,
+              note=f"defaults target={default[0]} min_tiles={default[1]}",
+              base=f"target={default[0]} min_tiles={default[1]}")
 
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
