@@ -90,6 +90,15 @@ __device__ __forceinline__ float fast_tanhf(float x) {
     return 1.f - 2.f * __builtin_amdgcn_rcpf(e + 1.f);
 }
 
+// Switches packed f32 ops off for one function (the pragma of
+// decode_paged_grouped.hip, per function): a kernel marked with it and
+// everything always_inline that it calls carry no v_pk_*_f32.
+#ifdef __HIP_DEVICE_COMPILE__
+#define RING_ATTN_NO_PACKED_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define RING_ATTN_NO_PACKED_F32
+#endif
+
 // cross-half (lane <-> lane^32) exchange via v_permlane32_swap — pure VALU,
 // no LDS round trip (a __shfl_xor(x, 32) lowers to ds_bpermute + addressing)
 __device__ __forceinline__ float cross_half(float x) {
@@ -323,6 +332,10 @@ struct DecodeParams {
     long chunks;            // kv-split S (0 = auto)
     const void* kscale;     // fp8 mode: e8m0 per kv row (B, HK, N)
     const void* vscale;     // fp8 mode: e8m0 per kv row (B, HK, N)
+    // logit capping (FwdParams' fields): sim = c * tanh(score * scale / c)
+    // before any mask; selects the SOFTCLAMP instantiation on the host
+    int softclamp;          // bool
+    float softclamp_value;  // c > 0
 };
 
 // Default kv-split S of every decode partial: ~512 keys per wave over the
@@ -379,6 +392,10 @@ struct PagedDecodeParams {
     int has_win;            // 0 = no window (win and kv_after unused)
     long win;               // >= 0
     const int* kv_after;    // int32 (B): tokens held by LATER ranks, or null (0)
+    // logit capping (FwdParams' fields): sim = c * tanh(score * scale / c)
+    // before any mask; selects the SOFTCLAMP instantiation on the host
+    int softclamp;          // bool
+    float softclamp_value;  // c > 0
 };
 
 void launch_decode_partial_paged(const PagedDecodeParams& p, int head_dim, bool fp8,
@@ -414,6 +431,10 @@ struct PagedGroupedDecodeParams {
     int has_window;         // 0 = no window (window and kv_after unused)
     long window;            // >= 0
     const int* kv_after;    // int32 (B): tokens held by LATER ranks, or null (0)
+    // logit capping (FwdParams' fields): sim = c * tanh(score * scale / c)
+    // before any mask; selects the SOFTCLAMP instantiation on the host
+    int softclamp;          // bool
+    float softclamp_value;  // c > 0
 };
 
 // the kv-split S the launcher uses (the binding sizes the partials with it)
@@ -440,6 +461,10 @@ struct GroupedDecodeParams {
     float scale;
     long n;
     long chunks;            // kv-split S (0 = auto from n)
+    // logit capping (FwdParams' fields): sim = c * tanh(score * scale / c)
+    // before any mask; selects the SOFTCLAMP instantiation on the host
+    int softclamp;          // bool
+    float softclamp_value;  // c > 0
 };
 
 // row tiles per workgroup and the kv-split S the launcher uses (the binding
@@ -498,6 +523,10 @@ struct PagedPrefillParams {
     // partials are per slot: o (slots, H, D, 256), m and l (slots, H, 256)
     const int* units;       // int32 (n_units, PAGED_UNIT_INTS), see below
     int n_units, n_slots;
+    // logit capping (FwdParams' fields): sim = c * tanh(score * scale / c)
+    // before any mask; selects the SOFTCLAMP instantiation on the host
+    int softclamp;          // bool
+    float softclamp_value;  // c > 0
 };
 
 // One work unit of the varlen paged prefill: one 256-row q tile of one

@@ -10,7 +10,7 @@
 // the two length vectors; the algebra stays in attn_mask.h.
 //
 // The tile loop from the barrier downward is a COPY of attn_fwd_body.inc
-// without softclamp, bias, kmask, ticks and ablate.  attn_fwd.hip and its
+// without bias, kmask, ticks and ablate.  attn_fwd.hip and its
 // body are the headline kernel and their codegen is fragile against
 // refactoring (see the body's header), so the copy is the accepted cost, as
 // for the fp8 and v2 forwards.  What differs from the dense kernel:
@@ -44,6 +44,11 @@
 //     attn_fwd_merge_units (below) combines them.  These kernels carry no
 //     packed f32 op: the two products the compiler would pack go through
 //     mul_f32.
+//   * SOFTCLAMP (logit capping): the dense body's arms, x = c * log2e *
+//     tanh(s * scale / c) on every score before the mask, in one pass with the
+//     max on full tiles, and exp2(x - m) with no scale left to fold.  These
+//     instantiations, grid or UNITS, keep their f32 products single-issue
+//     like the UNITS ones.
 // Causal pairing is not used: the per-sequence diagonals differ.
 
 #include <hip/hip_runtime.h>
@@ -122,9 +127,10 @@ __device__ __forceinline__ StagedChunk<FP8> pool_chunk(const void* pool, const v
 
 }  // namespace
 
-template <int D, bool FP8, bool PAGE_TILE, bool UNITS = false>
+template <int D, bool FP8, bool PAGE_TILE, bool UNITS = false, bool SOFTCLAMP = false>
 __global__ __launch_bounds__(NTHREADS, 1) void attn_fwd_paged_kernel(PagedPrefillParams p) {
     static_assert(D % 32 == 0);
+    constexpr bool SINGLE = UNITS || SOFTCLAMP;   // f32 products through mul_f32
     constexpr int DBLK = D / 32;     // 32-d output blocks
     constexpr int KSTEPS = D / 16;   // QK^T k-steps
     constexpr int KVBLK = kvblk(D);
@@ -308,7 +314,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void attn_fwd_paged_kernel(PagedPrefil
         for (int r = 0; r < KREGS; ++r) {
             int c = tid + r * NTHREADS;
             int row = c / CH_PER_ROW, ch = c % CH_PER_ROW;
-            *(uint4*)(lds.k[par] + row * D + swz<D / 8>(row, ch) * 8) = kst[r].template bf16_bits<UNITS>();
+            *(uint4*)(lds.k[par] + row * D + swz<D / 8>(row, ch) * 8) = kst[r].template bf16_bits<SINGLE>();
         }
         #pragma unroll
         for (int r = 0; r < VREGS; ++r) {
@@ -318,8 +324,8 @@ __global__ __launch_bounds__(NTHREADS, 1) void attn_fwd_paged_kernel(PagedPrefil
             int jp = kperm_pair(c % (KVBLK / 2));
             int d0 = (c / (KVBLK / 2)) * 8;
             union { uint4 u; bf16x8 v; } va, vb;
-            va.u = vsta[r].template bf16_bits<UNITS>();
-            vb.u = vstb[r].template bf16_bits<UNITS>();
+            va.u = vsta[r].template bf16_bits<SINGLE>();
+            vb.u = vstb[r].template bf16_bits<SINGLE>();
             #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 int d = d0 + e;
@@ -333,6 +339,9 @@ __global__ __launch_bounds__(NTHREADS, 1) void attn_fwd_paged_kernel(PagedPrefil
     // 3-deep pipeline over DOUBLE-buffered LDS: one barrier per tile; LDS
     // writes and the next-next tile's HBM loads fully overlap the MFMAs
     const float scale2 = p.scale * LOG2E;    // softmax runs in the exp2 domain
+    // SOFTCLAMP: s -> tanh argument, tanh -> exp2-domain score
+    const float clamp_in = SOFTCLAMP ? p.scale * __builtin_amdgcn_rcpf(p.softclamp_value) : 0.f;
+    const float clamp_out = p.softclamp_value * LOG2E;
     if (t_lo < t_hi) {
         fetch_ids();
         load_tile();
@@ -377,21 +386,36 @@ __global__ __launch_bounds__(NTHREADS, 1) void attn_fwd_paged_kernel(PagedPrefil
         // tile) rather than branched — hoist to one scalar branch.
         float smax = MASK_VALUE_F;
         if (full_tile) {
-            // exp2+fma fold: fmax runs on RAW scores (scale2 > 0 is
-            // monotone); the scale is folded into the exp argument as a
-            // single v_fma below — saves one VALU per element
-            #pragma unroll
-            for (int kb = 0; kb < NBLK; ++kb)
+            if constexpr (!SOFTCLAMP) {
+                // exp2+fma fold: fmax runs on RAW scores (scale2 > 0 is
+                // monotone); the scale is folded into the exp argument as a
+                // single v_fma below — saves one VALU per element
                 #pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    smax = fmaxf(smax, s[kb][r]);
-            smax *= scale2;
+                for (int kb = 0; kb < NBLK; ++kb)
+                    #pragma unroll
+                    for (int r = 0; r < 16; ++r)
+                        smax = fmaxf(smax, s[kb][r]);
+                smax *= scale2;
+            } else {
+                #pragma unroll
+                for (int kb = 0; kb < NBLK; ++kb)
+                    #pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float x = mul_f32(clamp_out, fast_tanhf(mul_f32(s[kb][r], clamp_in)));
+                        s[kb][r] = x;
+                        smax = fmaxf(smax, x);
+                    }
+            }
         } else {
             #pragma unroll
             for (int kb = 0; kb < NBLK; ++kb)
                 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    float x = s[kb][r] * scale2;
+                    float x;
+                    if constexpr (SOFTCLAMP)
+                        x = mul_f32(clamp_out, fast_tanhf(mul_f32(s[kb][r], clamp_in)));
+                    else
+                        x = s[kb][r] * scale2;
                     long j = j0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
                     bool ok = M.attends(qpos_i, j, j <= jmax);
                     if (!ok) x = MASK_VALUE_F;
@@ -410,8 +434,8 @@ __global__ __launch_bounds__(NTHREADS, 1) void attn_fwd_paged_kernel(PagedPrefil
         // exp-domain max keeps those exps at 0 while leaving real rows
         // (|scores| << 1e37) untouched.
         const float m_exp = fmaxf(m_new, -1.7e38f);
-        // full tiles kept RAW scores: exp2(fma(s, scale2, -m))
-        const float escale = full_tile ? scale2 : 1.f;
+        // full tiles (no softclamp) kept RAW scores: exp2(fma(s, scale2, -m))
+        const float escale = (full_tile && !SOFTCLAMP) ? scale2 : 1.f;
         alignas(16) uint32_t pk[NBLK * 8];                          // packed bf16 pairs
         float partial[NBLK * 8];
         #pragma unroll
@@ -440,7 +464,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void attn_fwd_paged_kernel(PagedPrefil
                     // the one change between the two forms inside the loop:
                     // the UNITS kernels carry no packed f32 op (same IEEE
                     // product, bitwise equal)
-                    if constexpr (UNITS) o_acc[db][r] = mul_f32(o_acc[db][r], alpha);
+                    if constexpr (SINGLE) o_acc[db][r] = mul_f32(o_acc[db][r], alpha);
                     else o_acc[db][r] *= alpha;
                 }
             m_run = m_new;
@@ -520,7 +544,7 @@ __global__ __launch_bounds__(NTHREADS, 1) void attn_fwd_paged_kernel(PagedPrefil
             __bf16 four[4];
             #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                if constexpr (UNITS) four[e] = (__bf16)mul_f32(o_acc[db][g * 4 + e], inv_l);
+                if constexpr (SINGLE) four[e] = (__bf16)mul_f32(o_acc[db][g * 4 + e], inv_l);
                 else four[e] = (__bf16)(o_acc[db][g * 4 + e] * inv_l);
             }
             int d = db * 32 + 8 * g + 4 * lhi;
@@ -532,42 +556,39 @@ __global__ __launch_bounds__(NTHREADS, 1) void attn_fwd_paged_kernel(PagedPrefil
     }
 }
 
-template <int D, bool FP8>
+// page-tile and clamp switches of one (D, FP8, UNITS) family, picked on the host
+template <int D, bool FP8, bool UNITS>
 static void launch_paged_d(const PagedPrefillParams& p, dim3 grid, hipStream_t stream) {
     dim3 block(NTHREADS);
-    if ((1 << p.page_shift) >= kvblk(D))
-        hipLaunchKernelGGL((attn_fwd_paged_kernel<D, FP8, true>), grid, block, 0, stream, p);
+    const bool page_tile = (1 << p.page_shift) >= kvblk(D);
+    if (page_tile && !p.softclamp)
+        hipLaunchKernelGGL((attn_fwd_paged_kernel<D, FP8, true, UNITS>), grid, block, 0, stream, p);
+    else if (!p.softclamp)
+        hipLaunchKernelGGL((attn_fwd_paged_kernel<D, FP8, false, UNITS>), grid, block, 0, stream, p);
+    else if (page_tile)
+        hipLaunchKernelGGL((attn_fwd_paged_kernel<D, FP8, true, UNITS, true>), grid, block, 0, stream, p);
     else
-        hipLaunchKernelGGL((attn_fwd_paged_kernel<D, FP8, false>), grid, block, 0, stream, p);
+        hipLaunchKernelGGL((attn_fwd_paged_kernel<D, FP8, false, UNITS, true>), grid, block, 0, stream, p);
 }
 
 void launch_attn_fwd_paged(const PagedPrefillParams& p, int head_dim, bool fp8,
                            hipStream_t stream) {
     dim3 grid((unsigned)ceil_div(p.t, QROWS_WG), (unsigned)(p.b * p.h),
               (unsigned)(p.kv_split > 1 ? p.kv_split : 1));
-    if (head_dim == 64 && !fp8) launch_paged_d<64, false>(p, grid, stream);
-    else if (head_dim == 128 && !fp8) launch_paged_d<128, false>(p, grid, stream);
-    else if (head_dim == 64) launch_paged_d<64, true>(p, grid, stream);
-    else if (head_dim == 128) launch_paged_d<128, true>(p, grid, stream);
+    if (head_dim == 64 && !fp8) launch_paged_d<64, false, false>(p, grid, stream);
+    else if (head_dim == 128 && !fp8) launch_paged_d<128, false, false>(p, grid, stream);
+    else if (head_dim == 64) launch_paged_d<64, true, false>(p, grid, stream);
+    else if (head_dim == 128) launch_paged_d<128, true, false>(p, grid, stream);
     else __builtin_trap();   // unsupported head dim is a host-side error (bindings)
-}
-
-template <int D, bool FP8>
-static void launch_paged_units_d(const PagedPrefillParams& p, dim3 grid, hipStream_t stream) {
-    dim3 block(NTHREADS);
-    if ((1 << p.page_shift) >= kvblk(D))
-        hipLaunchKernelGGL((attn_fwd_paged_kernel<D, FP8, true, true>), grid, block, 0, stream, p);
-    else
-        hipLaunchKernelGGL((attn_fwd_paged_kernel<D, FP8, false, true>), grid, block, 0, stream, p);
 }
 
 void launch_attn_fwd_paged_units(const PagedPrefillParams& p, int head_dim, bool fp8,
                                  hipStream_t stream) {
     dim3 grid((unsigned)p.n_units, (unsigned)p.h);
-    if (head_dim == 64 && !fp8) launch_paged_units_d<64, false>(p, grid, stream);
-    else if (head_dim == 128 && !fp8) launch_paged_units_d<128, false>(p, grid, stream);
-    else if (head_dim == 64) launch_paged_units_d<64, true>(p, grid, stream);
-    else if (head_dim == 128) launch_paged_units_d<128, true>(p, grid, stream);
+    if (head_dim == 64 && !fp8) launch_paged_d<64, false, true>(p, grid, stream);
+    else if (head_dim == 128 && !fp8) launch_paged_d<128, false, true>(p, grid, stream);
+    else if (head_dim == 64) launch_paged_d<64, true, true>(p, grid, stream);
+    else if (head_dim == 128) launch_paged_d<128, true, true>(p, grid, stream);
     else __builtin_trap();
 }
 

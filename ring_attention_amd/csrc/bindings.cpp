@@ -339,6 +339,16 @@ struct DecodePartials {
     float scale;
 };
 
+// softclamp / softclamp_value of the serving kernels (FwdParams' names): the
+// flag picks the SOFTCLAMP instantiation, the value must be a positive cap
+#define SET_SOFTCLAMP(p, softclamp, value)                                           \
+    do {                                                                             \
+        TORCH_CHECK(!(softclamp) || ((value) > 0 && std::isfinite(value)),           \
+                    "softclamp_value must be positive and finite");                  \
+        (p).softclamp = (softclamp) ? 1 : 0;                                         \
+        (p).softclamp_value = (float)(value);                                        \
+    } while (0)
+
 static DecodePartials decode_partials(const at::Tensor& q, int64_t span,
                                       int64_t chunks_in, double sm_scale) {
     const int64_t B = q.size(0), H = q.size(1), NQ = q.size(2), D = q.size(3);
@@ -354,7 +364,8 @@ static DecodePartials decode_partials(const at::Tensor& q, int64_t span,
 }
 
 std::vector<at::Tensor> decode_partial(at::Tensor q, at::Tensor k, at::Tensor v,
-                                       double sm_scale, int64_t chunks_in) {
+                                       double sm_scale, int64_t chunks_in,
+                                       bool softclamp, double softclamp_value) {
     // q (B,HQ,NQ,D); k,v (B,HK,N,D) bf16 — NQ query tokens (speculative /
     // tree heads), HQ % HK == 0 (GQA, tile pairing qh % hk)
     // -> (out fp32 (S,B,HQ,NQ,D), lse fp32 (S,B,HQ,NQ,1)): S kv-chunk
@@ -371,6 +382,7 @@ std::vector<at::Tensor> decode_partial(at::Tensor q, at::Tensor k, at::Tensor v,
     p.b = (int)B; p.h = (int)H; p.hk = (int)HK; p.nq = (int)NQ; p.n = N;
     p.scale = r.scale;
     p.chunks = r.chunks;
+    SET_SOFTCLAMP(p, softclamp, softclamp_value);
     launch_decode_partial(p, (int)D, at::hip::getCurrentHIPStream());
     TORCH_CHECK(hipGetLastError() == hipSuccess, "decode launch failed");
     return {r.out, r.lse};
@@ -515,7 +527,8 @@ std::vector<at::Tensor> quantize_kv_cache(at::Tensor k, at::Tensor v) {
 
 std::vector<at::Tensor> decode_partial_fp8(at::Tensor q, at::Tensor k8, at::Tensor v8,
                                            at::Tensor ks, at::Tensor vs,
-                                           double sm_scale, int64_t chunks_in) {
+                                           double sm_scale, int64_t chunks_in,
+                                           bool softclamp, double softclamp_value) {
     // FP8 KV-cache decode partial: q bf16 (B,HQ,NQ,D); k8/v8 e4m3 u8
     // (B,HK,N,D) with per-row e8m0 scales ks/vs (B,HK,N).  Same output
     // contract as decode_partial: (out fp32 (S,B,HQ,NQ,D), lse (S,B,HQ,NQ,1)).
@@ -536,6 +549,7 @@ std::vector<at::Tensor> decode_partial_fp8(at::Tensor q, at::Tensor k8, at::Tens
     p.b = (int)B; p.h = (int)H; p.hk = (int)HK; p.nq = (int)NQ; p.n = N;
     p.scale = r.scale;
     p.chunks = r.chunks;
+    SET_SOFTCLAMP(p, softclamp, softclamp_value);
     launch_decode_partial_fp8(p, (int)D, at::hip::getCurrentHIPStream());
     TORCH_CHECK(hipGetLastError() == hipSuccess, "decode fp8 launch failed");
     return {r.out, r.lse};
@@ -613,7 +627,8 @@ std::vector<at::Tensor> decode_partial_paged(
     std::optional<at::Tensor> k_scales, std::optional<at::Tensor> v_scales,
     at::Tensor block_table, at::Tensor seq_lens, int64_t max_seq_len,
     double sm_scale, bool causal, int64_t chunks_in,
-    bool has_win, int64_t win, std::optional<at::Tensor> kv_after) {
+    bool has_win, int64_t win, std::optional<at::Tensor> kv_after,
+    bool softclamp, double softclamp_value) {
     // q bf16 (B,HQ,NQ,D); pages (P,HK,PS,D) bf16, or uint8 e4m3 with per-row
     // e8m0 scales (P,HK,PS) — the page dtype selects the fp8 kernel;
     // block_table int32 (B,max_pages), seq_lens int32 (B,).  max_seq_len is
@@ -672,6 +687,7 @@ std::vector<at::Tensor> decode_partial_paged(
     p.has_win = has_win ? 1 : 0;
     p.win = has_win ? win : 0;
     p.kv_after = has_win && kv_after.has_value() ? kv_after->data_ptr<int>() : nullptr;
+    SET_SOFTCLAMP(p, softclamp, softclamp_value);
     launch_decode_partial_paged(p, (int)D, fp8, at::hip::getCurrentHIPStream());
     TORCH_CHECK(hipGetLastError() == hipSuccess, "paged decode launch failed");
     return {r.out, r.lse};
@@ -682,7 +698,8 @@ std::vector<at::Tensor> decode_partial_paged_grouped(
     std::optional<at::Tensor> k_scales, std::optional<at::Tensor> v_scales,
     at::Tensor block_table, at::Tensor seq_lens, int64_t max_seq_len,
     double sm_scale, int64_t chunks_in, std::optional<at::Tensor> tree_bits,
-    bool has_window, int64_t window, std::optional<at::Tensor> kv_after) {
+    bool has_window, int64_t window, std::optional<at::Tensor> kv_after,
+    bool softclamp, double softclamp_value) {
     // operands as decode_partial_paged; tree_bits int32 (B,NQ,2): 64 mask
     // bits per (sequence, draft), low word first (bit t = draft t visible).
     // The caller has checked on the host that every sequence with a mask
@@ -740,6 +757,7 @@ std::vector<at::Tensor> decode_partial_paged_grouped(
     p.num_pages = (int)k_pages.size(0);
     p.chunk_major = B > 1 ? 1 : 0;
     p.scale = r.scale;
+    SET_SOFTCLAMP(p, softclamp, softclamp_value);
     launch_decode_partial_paged_grouped(p, (int)D, fp8, at::hip::getCurrentHIPStream());
     TORCH_CHECK(hipGetLastError() == hipSuccess, "grouped paged decode launch failed");
     return {r.out, r.lse};
@@ -748,7 +766,8 @@ std::vector<at::Tensor> decode_partial_paged_grouped(
 std::vector<at::Tensor> decode_partial_grouped(
     at::Tensor q, at::Tensor k, at::Tensor v,
     std::optional<at::Tensor> kscale, std::optional<at::Tensor> vscale,
-    double sm_scale, int64_t chunks_in, std::optional<at::Tensor> tree_bits) {
+    double sm_scale, int64_t chunks_in, std::optional<at::Tensor> tree_bits,
+    bool softclamp, double softclamp_value) {
     // q bf16 (B,HQ,NQ,D); k, v (B,HK,N,D) bf16, or e4m3 bytes with e8m0 row
     // scales kscale / vscale (B,HK,N); tree_bits int32 (B,NQ,2) as in
     // decode_partial_paged_grouped: the last NQ keys are the drafts.  Same
@@ -801,6 +820,7 @@ std::vector<at::Tensor> decode_partial_grouped(
     p.out = r.out.data_ptr<float>(); p.lse = r.lse.data_ptr<float>();
     p.chunk_major = B > 1 ? 1 : 0;
     p.scale = r.scale;
+    SET_SOFTCLAMP(p, softclamp, softclamp_value);
     launch_decode_partial_grouped(p, (int)D, fp8, at::hip::getCurrentHIPStream());
     TORCH_CHECK(hipGetLastError() == hipSuccess, "grouped decode launch failed");
     return {r.out, r.lse};
@@ -848,7 +868,8 @@ void attn_fwd_paged(
     std::optional<at::Tensor> out, std::optional<at::Tensor> lse,
     std::optional<at::Tensor> o_part, std::optional<at::Tensor> m_part,
     std::optional<at::Tensor> l_part,
-    double scale, bool causal, int64_t win, bool has_win, int64_t kv_split) {
+    double scale, bool causal, int64_t win, bool has_win, int64_t kv_split,
+    bool softclamp, double softclamp_value) {
     // q bf16 (B,T,H,D); pool operands as decode_partial_paged; q_lens int32
     // (B,).  kv_split <= 1 writes out bf16 (B,T,H,D) + lse fp32 (B,H,T);
     // kv_split > 1 writes the (S,B,H,D,T) + m,l partials for attn_fwd_merge.
@@ -900,6 +921,7 @@ void attn_fwd_paged(
     p.causal = causal ? 1 : 0; p.has_win = has_win ? 1 : 0; p.win = win;
     p.scale = (float)scale;
     p.kv_split = (int)kv_split;
+    SET_SOFTCLAMP(p, softclamp, softclamp_value);
     launch_attn_fwd_paged(p, (int)D, fp8, at::hip::getCurrentHIPStream());
     TORCH_CHECK(hipGetLastError() == hipSuccess, "paged prefill launch failed");
 }
@@ -911,7 +933,8 @@ void attn_fwd_paged_units(
     at::Tensor units, at::Tensor out, at::Tensor lse,
     std::optional<at::Tensor> o_part, std::optional<at::Tensor> m_part,
     std::optional<at::Tensor> l_part,
-    double scale, bool causal, int64_t win, bool has_win) {
+    double scale, bool causal, int64_t win, bool has_win,
+    bool softclamp, double softclamp_value) {
     // q, out bf16 packed (total,H,D); lse fp32 (H,total); pool operands and
     // q_lens as attn_fwd_paged; units int32 (U, PAGED_UNIT_INTS).  Units with
     // count > 1 write slot slot0 + z of o_part (slots,H,D,256) and m_part,
@@ -977,6 +1000,7 @@ void attn_fwd_paged_units(
     p.scale = (float)scale;
     p.kv_split = 1;
     p.n_units = (int)U;
+    SET_SOFTCLAMP(p, softclamp, softclamp_value);
     launch_attn_fwd_paged_units(p, (int)D, fp8, at::hip::getCurrentHIPStream());
     TORCH_CHECK(hipGetLastError() == hipSuccess, "paged prefill units launch failed");
 }
@@ -1064,7 +1088,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::arg("dk"), py::arg("dv"), py::arg("dq") = std::nullopt);
     mod.def("decode_partial", &ring_attn::decode_partial, "CDNA4 single-query decode partial",
             py::arg("q"), py::arg("k"), py::arg("v"), py::arg("sm_scale") = -1.0,
-            py::arg("chunks") = 0);
+            py::arg("chunks") = 0, py::arg("softclamp") = false,
+            py::arg("softclamp_value") = 50.0);
     mod.def("attn_fwd_fp8", &ring_attn::attn_fwd_fp8,
             "CDNA4 MX-FP8 serving forward (e4m3 + e8m0 row scales)",
             py::arg("q8"), py::arg("k8"), py::arg("v8t"), py::arg("qs"),
@@ -1082,7 +1107,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
     mod.def("decode_partial_fp8", &ring_attn::decode_partial_fp8,
             "CDNA4 FP8 KV-cache decode partial",
             py::arg("q"), py::arg("k8"), py::arg("v8"), py::arg("ks"),
-            py::arg("vs"), py::arg("sm_scale") = -1.0, py::arg("chunks") = 0);
+            py::arg("vs"), py::arg("sm_scale") = -1.0, py::arg("chunks") = 0, py::arg("softclamp") = false,
+            py::arg("softclamp_value") = 50.0);
     mod.def("decode_merge", &ring_attn::decode_merge,
             "fused kv-chunk partial merge for decode");
     mod.def("decode_partial_paged", &ring_attn::decode_partial_paged,
@@ -1092,7 +1118,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::arg("seq_lens"), py::arg("max_seq_len"),
             py::arg("sm_scale") = -1.0, py::arg("causal") = false,
             py::arg("chunks") = 0, py::arg("has_win") = false,
-            py::arg("win") = 0, py::arg("kv_after") = py::none());
+            py::arg("win") = 0, py::arg("kv_after") = py::none(), py::arg("softclamp") = false,
+            py::arg("softclamp_value") = 50.0);
     mod.def("decode_partial_paged_grouped", &ring_attn::decode_partial_paged_grouped,
             "CDNA4 grouped MFMA paged decode partial with an optional token-tree mask",
             py::arg("q"), py::arg("k_pages"), py::arg("v_pages"),
@@ -1100,14 +1127,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::arg("seq_lens"), py::arg("max_seq_len"),
             py::arg("sm_scale") = -1.0, py::arg("chunks") = 0,
             py::arg("tree_bits") = py::none(), py::arg("has_window") = false,
-            py::arg("window") = 0, py::arg("kv_after") = py::none());
+            py::arg("window") = 0, py::arg("kv_after") = py::none(), py::arg("softclamp") = false,
+            py::arg("softclamp_value") = 50.0);
     mod.def("decode_partial_grouped", &ring_attn::decode_partial_grouped,
             "CDNA4 grouped MFMA decode partial over the dense cache (bf16 or fp8), "
             "optional token-tree mask",
             py::arg("q"), py::arg("k"), py::arg("v"),
             py::arg("kscale") = py::none(), py::arg("vscale") = py::none(),
             py::arg("sm_scale") = -1.0, py::arg("chunks") = 0,
-            py::arg("tree_bits") = py::none());
+            py::arg("tree_bits") = py::none(), py::arg("softclamp") = false,
+            py::arg("softclamp_value") = 50.0);
     mod.def("paged_kv_append", &ring_attn::paged_kv_append,
             "write new tokens into a paged KV cache (fused fp8 quantisation)",
             py::arg("k_new"), py::arg("v_new"), py::arg("k_pages"),
@@ -1120,7 +1149,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::arg("seq_lens"), py::arg("q_lens"), py::arg("out"), py::arg("lse"),
             py::arg("o_part"), py::arg("m_part"), py::arg("l_part"),
             py::arg("scale"), py::arg("causal"), py::arg("win"),
-            py::arg("has_win"), py::arg("kv_split"));
+            py::arg("has_win"), py::arg("kv_split"), py::arg("softclamp") = false,
+            py::arg("softclamp_value") = 50.0);
     mod.def("attn_fwd_paged_units", &ring_attn::attn_fwd_paged_units,
             "CDNA4 varlen paged prefill: packed q, one workgroup per work unit",
             py::arg("q"), py::arg("k_pages"), py::arg("v_pages"),
@@ -1128,7 +1158,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::arg("seq_lens"), py::arg("q_lens"), py::arg("units"),
             py::arg("out"), py::arg("lse"),
             py::arg("o_part"), py::arg("m_part"), py::arg("l_part"),
-            py::arg("scale"), py::arg("causal"), py::arg("win"), py::arg("has_win"));
+            py::arg("scale"), py::arg("causal"), py::arg("win"), py::arg("has_win"), py::arg("softclamp") = false,
+            py::arg("softclamp_value") = 50.0);
     mod.def("attn_fwd_merge_units", &ring_attn::attn_fwd_merge_units,
             "merge the work units' shares into packed out / lse",
             py::arg("o_part"), py::arg("m_part"), py::arg("l_part"),

@@ -16,8 +16,12 @@ namespace ring_attn {
 // FP8 = the KV cache is 8-bit (half the HBM bytes — decode is bandwidth-
 // bound, measured 1.5-1.6 TB/s on the bf16 stream): k/v are e4m3 rows with
 // one e8m0 scale per kv row (kscale/vscale); q stays bf16.
-template <int D, bool FP8>
-__global__ __launch_bounds__(256) void decode_partial_kernel(DecodeParams p) {
+//
+// The body is shared by two kernels: decode_partial_kernel, and with SOFTCLAMP
+// (logit capping, decode_common.h) decode_partial_softclamp_kernel, which is
+// built without packed f32 ops.
+template <int D, bool FP8, bool SOFTCLAMP>
+__device__ __forceinline__ void decode_partial_rows(const DecodeParams& p) {
     // one wave per (b, q-head, query token); 4 waves per block; blockIdx.y
     // splits the KV range into `chunks` partials (merged on the host) so
     // long sequences use the whole chip.  Multi-query (speculative / tree
@@ -35,22 +39,38 @@ __global__ __launch_bounds__(256) void decode_partial_kernel(DecodeParams p) {
     const long j_hi = min(p.n, j_lo + per);
     const long kv0 = ((long)r.b * p.hk + r.hk) * p.n;   // first row of this kv head
 
+    const float c = p.softclamp_value;
+    const float rcp_c = SOFTCLAMP ? __builtin_amdgcn_rcpf(c) : 0.f;
+
     DecodeState<D> st;
     st.init((const __bf16*)p.q + ((long)r.bh * p.nq + r.iq) * D);
     for (long j = j_lo + lane; j < j_hi; j += 64) {
         const long row = kv0 + j;
         if constexpr (FP8) {
-            st.fold_fp8((const unsigned char*)p.k + row * D,
-                        (const unsigned char*)p.v + row * D,
-                        (const unsigned char*)p.kscale + row,
-                        (const unsigned char*)p.vscale + row, p.scale);
+            st.template fold_fp8<SOFTCLAMP>((const unsigned char*)p.k + row * D,
+                                            (const unsigned char*)p.v + row * D,
+                                            (const unsigned char*)p.kscale + row,
+                                            (const unsigned char*)p.vscale + row,
+                                            p.scale, c, rcp_c);
         } else {
-            st.fold_bf16((const __bf16*)p.k + row * D, (const __bf16*)p.v + row * D,
-                         p.scale);
+            st.template fold_bf16<SOFTCLAMP>((const __bf16*)p.k + row * D,
+                                             (const __bf16*)p.v + row * D,
+                                             p.scale, c, rcp_c);
         }
     }
     const long slot = (long)chunk * rows + (long)r.bh * p.nq + r.iq;
     st.finish(lane, p.out + slot * D, p.lse + slot);
+}
+
+template <int D, bool FP8>
+__global__ __launch_bounds__(256) void decode_partial_kernel(DecodeParams p) {
+    decode_partial_rows<D, FP8, false>(p);
+}
+
+template <int D, bool FP8>
+__global__ __launch_bounds__(256) RING_ATTN_NO_PACKED_F32
+void decode_partial_softclamp_kernel(DecodeParams p) {
+    decode_partial_rows<D, FP8, true>(p);
 }
 
 template <bool FP8>
@@ -60,10 +80,14 @@ static void launch_decode_partial_t(const DecodeParams& p, int head_dim, hipStre
     long chunks = p.chunks > 0 ? p.chunks : decode_default_chunks(p.n, waves);
     dim3 grid((waves + 3) / 4, (unsigned)chunks);
     dim3 block(256);
-    if (head_dim == 64) {
+    if (head_dim == 64 && !p.softclamp) {
         hipLaunchKernelGGL((decode_partial_kernel<64, FP8>), grid, block, 0, stream, p);
-    } else if (head_dim == 128) {
+    } else if (head_dim == 128 && !p.softclamp) {
         hipLaunchKernelGGL((decode_partial_kernel<128, FP8>), grid, block, 0, stream, p);
+    } else if (head_dim == 64) {
+        hipLaunchKernelGGL((decode_partial_softclamp_kernel<64, FP8>), grid, block, 0, stream, p);
+    } else if (head_dim == 128) {
+        hipLaunchKernelGGL((decode_partial_softclamp_kernel<128, FP8>), grid, block, 0, stream, p);
     } else {
         __builtin_trap();
     }

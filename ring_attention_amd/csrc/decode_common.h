@@ -53,9 +53,14 @@ struct DecodeState {
         for (int d = 0; d < D; ++d) acc[d] = 0.f;
     }
 
-    // one bf16 key row: score and value pass fused online, 16-byte loads
+    // one bf16 key row: score and value pass fused online, 16-byte loads.
+    // SOFTCLAMP caps the scaled score, s = c * tanh(s / c) (the training
+    // kernels' fast_tanhf), before it meets the running max; rcp_c = 1 / c is
+    // the caller's, computed once per wave.
+    template <bool SOFTCLAMP = false>
     __device__ __forceinline__ void fold_bf16(const __bf16* krow, const __bf16* vrow,
-                                              float scale) {
+                                              float scale, float c = 0.f,
+                                              float rcp_c = 0.f) {
         float s = 0.f;
         #pragma unroll
         for (int d = 0; d < D; d += 8) {
@@ -64,6 +69,7 @@ struct DecodeState {
             for (int e = 0; e < 8; ++e) s += qreg[d + e] * (float)kv8[e];
         }
         s *= scale;
+        if constexpr (SOFTCLAMP) s = c * fast_tanhf(s * rcp_c);
         float m_new = fmaxf(m, s);
         float alpha = __expf(m - m_new);
         float w = __expf(s - m_new);
@@ -80,11 +86,14 @@ struct DecodeState {
     // one e4m3 key row with ONE e8m0 scale per row (*ksc, *vsc): the k scale
     // folds into the score (s_true = 2^ek * dot(q, k8)) and the v scale into
     // the softmax weight (acc += (w * 2^ev) * v8) — the same fp32 math as the
-    // bf16 row, only the loads halve
+    // bf16 row, only the loads halve.  SOFTCLAMP caps the true score, after
+    // the key scale.
+    template <bool SOFTCLAMP = false>
     __device__ __forceinline__ void fold_fp8(const unsigned char* krow,
                                              const unsigned char* vrow,
                                              const unsigned char* ksc,
-                                             const unsigned char* vsc, float scale) {
+                                             const unsigned char* vsc, float scale,
+                                             float c = 0.f, float rcp_c = 0.f) {
         float s = 0.f;
         #pragma unroll
         for (int d = 0; d < D; d += 16) {
@@ -99,6 +108,7 @@ struct DecodeState {
             }
         }
         s *= scale * exp2f((float)*ksc - 127.f);
+        if constexpr (SOFTCLAMP) s = c * fast_tanhf(s * rcp_c);
         float m_new = fmaxf(m, s);
         float alpha = __expf(m - m_new);
         float w = __expf(s - m_new) * exp2f((float)*vsc - 127.f);

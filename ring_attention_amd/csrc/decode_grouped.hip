@@ -38,6 +38,8 @@
 //     tree_bits[b][iq] is set, keys below P0 to every row.  Blocks that end at
 //     or below P0 take the open arm.  Without tree_bits P0 = N.  Keys at or
 //     beyond the chunk's end are zero-filled without forming an address.
+//   * SOFTCLAMP: decode_paged_grouped.hip's, per tile: x = c * log2e *
+//     tanh(s * scale / c) in both arms, max on x, exp2(x - m).
 // No window, no kv_after: a dense cache can be sliced by the caller.
 // The partial contract is decode.hip's (out fp32 (S,B,HQ,NQ,D), lse fp32
 // (S,B,HQ,NQ,1), out = 0 and lse = MASK_VALUE_F where a row saw no key), so
@@ -103,7 +105,7 @@ __device__ __forceinline__ DenseChunk<FP8> dense_chunk(const void* cache, const 
 
 }  // namespace
 
-template <int D, bool FP8, int TILES>
+template <int D, bool FP8, int TILES, bool SOFTCLAMP>
 __global__ __launch_bounds__(DG_WAVES * 64)
 // d 64, two tiles: fits 2 waves per SIMD when asked to (no scratch); the other
 // instantiations keep the allocator's own choice
@@ -250,6 +252,9 @@ void decode_partial_grouped_kernel(GroupedDecodeParams p) {
     }
 
     const float scale2 = p.scale * LOG2E;
+    // SOFTCLAMP: s -> tanh argument, tanh -> exp2-domain score
+    const float clamp_in = SOFTCLAMP ? p.scale * __builtin_amdgcn_rcpf(p.softclamp_value) : 0.f;
+    const float clamp_out = p.softclamp_value * LOG2E;
     const int nt = (int)(n - P0);               // drafts cached (0 without a mask)
     long j0 = j_lo + wid * DG_TILE;
     if (j0 < j_hi) {
@@ -284,10 +289,11 @@ void decode_partial_grouped_kernel(GroupedDecodeParams p) {
         }
 
         // a block below P0 is visible to every row and keeps raw scores (the
-        // scale folds into the exp argument)
+        // scale folds into the exp argument); clamped scores are final in
+        // either arm
         const bool open_block = j0 + DG_TILE <= P0;
         const int t0 = (int)(j0 - P0) + 4 * lhi;    // draft index of reg 0's key
-        const float escale = open_block ? scale2 : 1.f;
+        const float escale = (open_block && !SOFTCLAMP) ? scale2 : 1.f;
 
         #pragma unroll
         for (int t = 0; t < TILES; ++t) {
@@ -309,16 +315,31 @@ void decode_partial_grouped_kernel(GroupedDecodeParams p) {
             // ---- scale, mask
             float smax = MASK_VALUE_F;
             if (open_block) {
-                #pragma unroll
-                for (int r = 0; r < 16; ++r) smax = fmaxf(smax, s[r]);
-                smax *= scale2;
+                if constexpr (SOFTCLAMP) {
+                    #pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        s[r] = clamp_out * fast_tanhf(s[r] * clamp_in);
+                        smax = fmaxf(smax, s[r]);
+                    }
+                } else {
+                    #pragma unroll
+                    for (int r = 0; r < 16; ++r) smax = fmaxf(smax, s[r]);
+                    smax *= scale2;
+                }
             } else {
                 const unsigned long long bt = bits[t];
                 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int td = t0 + (r & 3) + 8 * (r >> 2);
                     const bool ok = td < 0 || (td < nt && ((bt >> (td & 63)) & 1));
-                    const float x = ok ? s[r] * scale2 : MASK_VALUE_F;
+                    float x;
+                    if constexpr (SOFTCLAMP) {
+                        // clamped before the test, as in the forward
+                        x = clamp_out * fast_tanhf(s[r] * clamp_in);
+                        if (!ok) x = MASK_VALUE_F;
+                    } else {
+                        x = ok ? s[r] * scale2 : MASK_VALUE_F;
+                    }
                     s[r] = x;
                     smax = fmaxf(smax, x);
                 }
@@ -475,8 +496,14 @@ void launch_decode_partial_grouped(const GroupedDecodeParams& p, int head_dim, b
     dim3 grid((unsigned)(p.b * p.hk * groups), (unsigned)grouped_decode_chunks(p, head_dim));
     dim3 block(DG_WAVES * 64);
 #define LAUNCH_DG(D_, FP8_, T_)                                                         \
-    hipLaunchKernelGGL((decode_partial_grouped_kernel<D_, FP8_, T_>), grid, block, 0,   \
-                       stream, p)
+    do {                                                                                \
+        if (p.softclamp)                                                                \
+            hipLaunchKernelGGL((decode_partial_grouped_kernel<D_, FP8_, T_, true>),     \
+                               grid, block, 0, stream, p);                              \
+        else                                                                            \
+            hipLaunchKernelGGL((decode_partial_grouped_kernel<D_, FP8_, T_, false>),    \
+                               grid, block, 0, stream, p);                              \
+    } while (0)
 #define LAUNCH_DG_FP8(D_, T_)                                                           \
     do { if (fp8) LAUNCH_DG(D_, true, T_); else LAUNCH_DG(D_, false, T_); } while (0)
     if (head_dim == 64 && per_wg == 1) LAUNCH_DG_FP8(64, 1);

@@ -52,6 +52,10 @@
 //     tokens; key P0 + t (P0 = len - nq) is visible to draft iq iff bit t of
 //     tree_bits[b][iq] is set, keys below P0 to every row.  Only blocks that
 //     reach beyond P0 test per element.  Without tree_bits P0 = len.
+//   * SOFTCLAMP (logit capping, the training kernels' definition): every
+//     score becomes x = c * log2e * tanh(s * scale / c) before the mask, in
+//     both arms; the max is taken on x and the exponent is exp2(x - m), with
+//     no scale left to fold.  scale / c and c * log2e are wave-uniform.
 // The partial contract is decode_paged.hip's (out fp32 (S,B,HQ,NQ,D), lse fp32
 // (S,B,HQ,NQ,1), out = 0 and lse = MASK_VALUE_F where a row saw no key), so
 // decode_merge and the cross-rank merge are reused unchanged.
@@ -122,7 +126,7 @@ __device__ __forceinline__ GroupedChunk<FP8> grouped_pool_chunk(
 
 }  // namespace
 
-template <int D, bool FP8, bool WIN>
+template <int D, bool FP8, bool WIN, bool SOFTCLAMP>
 __global__ __launch_bounds__(GWAVES * 64)
 void decode_partial_paged_grouped_kernel(PagedGroupedDecodeParams p) {
     static_assert(D == 64 || D == 128);
@@ -268,6 +272,9 @@ void decode_partial_paged_grouped_kernel(PagedGroupedDecodeParams p) {
     }
 
     const float scale2 = p.scale * LOG2E;
+    // SOFTCLAMP: s -> tanh argument, tanh -> exp2-domain score
+    const float clamp_in = SOFTCLAMP ? p.scale * __builtin_amdgcn_rcpf(p.softclamp_value) : 0.f;
+    const float clamp_out = p.softclamp_value * LOG2E;
     long j0 = j_lo + wid * GTILE;
     // lo_min < base + GPASS: only the first pass holds blocks below lo_min
     if constexpr (WIN) if (j0 + GTILE <= lo_min) j0 += GPASS;
@@ -300,13 +307,22 @@ void decode_partial_paged_grouped_kernel(PagedGroupedDecodeParams p) {
         }
 
         // ---- scale, mask.  A block below P0 is visible to every row and
-        // keeps raw scores (the scale folds into the exp argument).
+        // keeps raw scores (the scale folds into the exp argument); clamped
+        // scores are final in either arm.
         const bool open_block = j0 + GTILE <= P0 && (!WIN || j0 >= lo_max);
         float smax = MASK_VALUE_F;
         if (open_block) {
-            #pragma unroll
-            for (int r = 0; r < 16; ++r) smax = fmaxf(smax, s[r]);
-            smax *= scale2;
+            if constexpr (SOFTCLAMP) {
+                #pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    s[r] = clamp_out * fast_tanhf(s[r] * clamp_in);
+                    smax = fmaxf(smax, s[r]);
+                }
+            } else {
+                #pragma unroll
+                for (int r = 0; r < 16; ++r) smax = fmaxf(smax, s[r]);
+                smax *= scale2;
+            }
         } else {
             const int t0 = (int)(j0 - P0) + 4 * lhi;   // draft index of reg 0's key
             const int nt = (int)(len - P0);            // drafts cached (0 without a mask)
@@ -315,7 +331,14 @@ void decode_partial_paged_grouped_kernel(PagedGroupedDecodeParams p) {
                 const int t = t0 + (r & 3) + 8 * (r >> 2);
                 const bool ok = (!WIN || t >= tl)
                                 && (t < 0 || (t < nt && ((bits >> (t & 63)) & 1)));
-                const float x = ok ? s[r] * scale2 : MASK_VALUE_F;
+                float x;
+                if constexpr (SOFTCLAMP) {
+                    // clamped before the test, as in the forward
+                    x = clamp_out * fast_tanhf(s[r] * clamp_in);
+                    if (!ok) x = MASK_VALUE_F;
+                } else {
+                    x = ok ? s[r] * scale2 : MASK_VALUE_F;
+                }
                 s[r] = x;
                 smax = fmaxf(smax, x);
             }
@@ -328,7 +351,7 @@ void decode_partial_paged_grouped_kernel(PagedGroupedDecodeParams p) {
         const float m_new = fmaxf(m_run, smax);
         const bool any_growth = __builtin_amdgcn_ballot_w64(smax > m_run) != 0;
         const float m_exp = fmaxf(m_new, -1.7e38f);
-        const float escale = open_block ? scale2 : 1.f;
+        const float escale = (open_block && !SOFTCLAMP) ? scale2 : 1.f;
         alignas(16) uint32_t pk[8];
         float partial[8];
         #pragma unroll
@@ -453,16 +476,21 @@ void launch_decode_partial_paged_grouped(const PagedGroupedDecodeParams& p, int 
     const long tiles = ((long)(p.h / p.hk) * p.nq + GTILE - 1) / GTILE;
     dim3 grid((unsigned)(p.b * p.hk * tiles), (unsigned)paged_grouped_chunks(p));
     dim3 block(GWAVES * 64);
-    // the window is a template switch: the unwindowed instantiations keep
-    // the code they had before the window existed
-#define LAUNCH_GROUPED(D_, FP8_)                                                        \
+    // the window and the clamp are template switches: the instantiations
+    // without them keep the code they had before either existed
+#define LAUNCH_GROUPED_W(D_, FP8_, WIN_)                                                \
     do {                                                                                \
-        if (p.has_window)                                                               \
-            hipLaunchKernelGGL((decode_partial_paged_grouped_kernel<D_, FP8_, true>),   \
+        if (p.softclamp)                                                                \
+            hipLaunchKernelGGL((decode_partial_paged_grouped_kernel<D_, FP8_, WIN_, true>),  \
                                grid, block, 0, stream, p);                              \
         else                                                                            \
-            hipLaunchKernelGGL((decode_partial_paged_grouped_kernel<D_, FP8_, false>),  \
+            hipLaunchKernelGGL((decode_partial_paged_grouped_kernel<D_, FP8_, WIN_, false>), \
                                grid, block, 0, stream, p);                              \
+    } while (0)
+#define LAUNCH_GROUPED(D_, FP8_)                                                        \
+    do {                                                                                \
+        if (p.has_window) LAUNCH_GROUPED_W(D_, FP8_, true);                             \
+        else LAUNCH_GROUPED_W(D_, FP8_, false);                                         \
     } while (0)
     if (head_dim == 64 && !fp8)
         LAUNCH_GROUPED(64, false);
@@ -475,6 +503,7 @@ void launch_decode_partial_paged_grouped(const PagedGroupedDecodeParams& p, int 
     else
         __builtin_trap();
 #undef LAUNCH_GROUPED
+#undef LAUNCH_GROUPED_W
 }
 
 }  // namespace ring_attn

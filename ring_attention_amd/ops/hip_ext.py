@@ -47,6 +47,6 @@ def require():
     return ext
 
 
-def decode_partial(q, k, v, sm_scale=-1.0):
+def decode_partial(q, k, v, sm_scale=-1.0, softclamp=False, softclamp_value=50.0):
     """Single-query decode partial via the HIP kernel: (out fp32, lse fp32)."""
-    return require().decode_partial(q, k, v, sm_scale)
+    return require().decode_partial(q, k, v, sm_scale, 0, softclamp, softclamp_value)

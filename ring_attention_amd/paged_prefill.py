@@ -23,6 +23,8 @@ import torch
 import torch.nn.functional as F
 from torch import Tensor
 
+from .tree_decode import _check_softclamp, _softclamp
+
 _ROWS_WG = 256          # q rows per workgroup (csrc/attn_mask.h ROWS_WG)
 _TARGET_WGS = 256       # one workgroup per CU
 _MAX_SPLIT = 16         # attn_fwd_merge holds at most 16 shares
@@ -59,7 +61,8 @@ def _host_q_lens(q_lens, b: int, t: int, seq_lens: list[int]) -> list[int]:
     return q_lens
 
 
-def _eager(q: Tensor, cache, q_lens: list[int], causal: bool, window):
+def _eager(q: Tensor, cache, q_lens: list[int], causal: bool, window,
+           softclamp_qk_sim: bool = False, softclamp_value: float = 50.0):
     """Same result from cache.gather, in fp32 (CPU / use_hip_kernel=False)."""
     b, t, h, d = q.shape
     groups = h // cache.kv_heads
@@ -74,7 +77,8 @@ def _eager(q: Tensor, cache, q_lens: list[int], causal: bool, window):
         kf, vf = cache.gather(i)
         kf = kf.float().repeat(groups, 1, 1)            # tile pairing qh % hk
         vf = vf.float().repeat(groups, 1, 1)
-        sim = torch.einsum("thd,hjd->htj", q[i, :ql].float(), kf) * d ** -0.5
+        sim = _softclamp(torch.einsum("thd,hjd->htj", q[i, :ql].float(), kf) * d ** -0.5,
+                         softclamp_qk_sim, softclamp_value)
         pos = (n - ql + torch.arange(ql, device=q.device))[:, None]
         j = torch.arange(n, device=q.device)[None, :]
         ok = torch.ones(ql, n, dtype=torch.bool, device=q.device)
@@ -101,6 +105,8 @@ def paged_prefill_attn(
     return_lse: bool = False,
     use_hip_kernel: bool | None = None,
     kv_split: int = 0,
+    softclamp_qk_sim: bool = False,
+    softclamp_value: float = 50.0,
 ):
     """Attention of a query chunk over a PagedKVCache (serving path, no autograd).
 
@@ -120,7 +126,13 @@ def paged_prefill_attn(
     computes the same from `cache.gather`.  `kv_split=0` picks the grid.z
     split automatically (`auto_kv_split`); a positive value forces it (tests,
     A/B runs).
+
+    `softclamp_qk_sim` / `softclamp_value` are ring_flash_attn's logit capping,
+    sim = c * tanh(q.k * d**-0.5 / c) before the masks, c = softclamp_value > 0
+    (ValueError otherwise), in the kernel and in the eager path.
     """
+    _check_softclamp("paged_prefill_attn", softclamp_qk_sim, softclamp_value)
+    clamp = (bool(softclamp_qk_sim), float(softclamp_value))
     if q.requires_grad:
         raise RuntimeError(
             "paged_prefill_attn is a serving path without a backward pass: "
@@ -152,7 +164,7 @@ def paged_prefill_attn(
              for n, ql in zip(cache.host_lens, lens)])
 
     if not (q.is_cuda and use_hip_kernel is not False):
-        out, lse = _eager(q, cache, lens, causal, window)
+        out, lse = _eager(q, cache, lens, causal, window, *clamp)
         return (out, lse) if return_lse else out
 
     from .ops import hip_ext
@@ -173,12 +185,12 @@ def paged_prefill_attn(
         m_part = torch.empty(split, b, h, t, device=q.device, dtype=torch.float32)
         l_part = torch.empty(split, b, h, t, device=q.device, dtype=torch.float32)
         ext.attn_fwd_paged(qb, *pool, None, None, o_part, m_part, l_part,
-                           d ** -0.5, causal, win, window is not None, split)
+                           d ** -0.5, causal, win, window is not None, split, *clamp)
         ext.attn_fwd_merge(o_part, m_part, l_part, None, None, None,
                            out, lse, split, b, h, kd, t, True, True)
     else:
         ext.attn_fwd_paged(qb, *pool, out, lse, None, None, None,
-                           d ** -0.5, causal, win, window is not None, 1)
+                           d ** -0.5, causal, win, window is not None, 1, *clamp)
     if d != kd:
         out = out[..., :d]
     return (out, lse) if return_lse else out
@@ -261,6 +273,8 @@ def paged_prefill_attn_varlen(
     return_lse: bool = False,
     use_hip_kernel: bool | None = None,
     unit_tiles: int = 0,
+    softclamp_qk_sim: bool = False,
+    softclamp_value: float = 50.0,
 ):
     """`paged_prefill_attn` for packed queries, balanced over ragged batches.
 
@@ -268,7 +282,8 @@ def paged_prefill_attn_varlen(
     [cu[i], cu[i] + q_lens[i]) with cu the running sum of `q_lens` (a host
     list or int tensor, 0 <= q_lens[i] <= seq_len[i], sum == total).
     Positions, `causal`, `window`, released pages, the qh % hk pairing, small
-    head dims and fp8 pools are `paged_prefill_attn`'s.
+    head dims, fp8 pools and `softclamp_qk_sim` / `softclamp_value` are
+    `paged_prefill_attn`'s.
 
     Returns out bf16 (total, h, d); with `return_lse` also lse fp32
     (h, total), natural log.  A row with no attendable key returns out == 0
@@ -286,6 +301,8 @@ def paged_prefill_attn_varlen(
     batch.
     """
     name = "paged_prefill_attn_varlen"
+    _check_softclamp(name, softclamp_qk_sim, softclamp_value)
+    clamp = (bool(softclamp_qk_sim), float(softclamp_value))
     if q.requires_grad:
         raise RuntimeError(
             f"{name} is a serving path without a backward pass: "
@@ -331,7 +348,7 @@ def paged_prefill_attn_varlen(
         for i, ql in enumerate(lens):
             qp[i, :ql] = q[row0:row0 + ql]
             row0 += ql
-        out_p, lse_p = _eager(qp, cache, lens, causal, window)
+        out_p, lse_p = _eager(qp, cache, lens, causal, window, *clamp)
         out = torch.cat([out_p[i, :ql] for i, ql in enumerate(lens)])
         lse = torch.cat([lse_p[i, :, :ql] for i, ql in enumerate(lens)], dim=1)
         return (out, lse) if return_lse else out
@@ -365,7 +382,8 @@ def paged_prefill_attn_varlen(
     ext.attn_fwd_paged_units(
         qb, cache.k_pages, cache.v_pages, cache.k_scales, cache.v_scales,
         cache.block_table, cache.seq_lens, q_lens_dev, units_dev, out, lse, *parts,
-        d ** -0.5, causal, 0 if window is None else int(window), window is not None)
+        d ** -0.5, causal, 0 if window is None else int(window), window is not None,
+        *clamp)
     if slots:
         ext.attn_fwd_merge_units(*parts, merges_dev, out, lse)
     if d != kd:

@@ -25,16 +25,34 @@ from torch import Tensor
 from .parallel import get_rank, get_world_size, is_distributed
 
 
+def _check_softclamp(name: str, softclamp_qk_sim: bool, softclamp_value: float) -> None:
+    if softclamp_qk_sim and not softclamp_value > 0:
+        raise ValueError(f"{name}: softclamp_value must be > 0 (got {softclamp_value})")
+
+
+def _softclamp(sim: Tensor, softclamp_qk_sim: bool, softclamp_value: float) -> Tensor:
+    """Logit capping of the scaled scores, before any mask (the training
+    kernels' definition): c * tanh(sim / c)."""
+    if not softclamp_qk_sim:
+        return sim
+    return softclamp_value * torch.tanh(sim / softclamp_value)
+
+
 def _local_decode_partial(q: Tensor, k: Tensor, v: Tensor,
                           use_hip_kernel: bool | None = None,
                           vis: Tensor | None = None,
-                          grouped: bool = False) -> tuple[Tensor, Tensor]:
+                          grouped: bool = False,
+                          softclamp_qk_sim: bool = False,
+                          softclamp_value: float = 50.0) -> tuple[Tensor, Tensor]:
     """Local flash-decode partial: (out fp32 (b,h,nq,dv), lse fp32 (b,h,nq,1)).
 
     `vis` ((b, nq, nq) bool, from _draft_visibility) makes the last nq keys
     the drafts' own tokens: row i attends key n - nq + t iff vis[:, i, t], and
     every key below n - nq.  `grouped` (implied by `vis`) takes the grouped
-    MFMA kernel (csrc/decode_grouped.hip) instead of the row kernel."""
+    MFMA kernel (csrc/decode_grouped.hip) instead of the row kernel.
+    `softclamp_qk_sim` caps the scaled scores at `softclamp_value` (see
+    tree_attn_decode) in either kernel and in the eager path."""
+    clamp = (bool(softclamp_qk_sim), float(softclamp_value))
     if q.is_cuda and use_hip_kernel is not False:
         from .ops import hip_ext
         if hip_ext.available():
@@ -51,13 +69,13 @@ def _local_decode_partial(q: Tensor, k: Tensor, v: Tensor,
                     kb.to(torch.bfloat16).contiguous(),
                     vb.to(torch.bfloat16).contiguous(),
                     None, None, d ** -0.5, 0,
-                    None if vis is None else _tree_bits(vis))
+                    None if vis is None else _tree_bits(vis), *clamp)
             else:
                 outs, lses = hip_ext.decode_partial(
                     qb.to(torch.bfloat16).contiguous(),
                     kb.to(torch.bfloat16).contiguous(),
                     vb.to(torch.bfloat16).contiguous(),
-                    sm_scale=d ** -0.5)
+                    d ** -0.5, *clamp)
             # fused S-chunk merge (the torch reduce expression costs more
             # dispatches than the decode kernel itself at S = 256)
             out, lse = hip_ext.require().decode_merge(outs, lses)
@@ -70,7 +88,7 @@ def _local_decode_partial(q: Tensor, k: Tensor, v: Tensor,
     if groups > 1:                      # tile GQA pairing (qh % hk)
         kf = kf.repeat(1, groups, 1, 1)
         vf = vf.repeat(1, groups, 1, 1)
-    sim = torch.einsum("bhid,bhjd->bhij", q.float(), kf) * scale
+    sim = _softclamp(torch.einsum("bhid,bhjd->bhij", q.float(), kf) * scale, *clamp)
     if vis is not None:                 # prefix open, drafts by mask (diagonal set)
         nq, n = q.shape[2], k.shape[2]
         masked = torch.zeros(q.shape[0], nq, n, dtype=torch.bool, device=q.device)
@@ -126,8 +144,17 @@ def tree_attn_decode(
     causal: bool = False,
     tree_mask: Tensor | None = None,
     grouped: bool | None = None,
+    softclamp_qk_sim: bool = False,
+    softclamp_value: float = 50.0,
 ) -> Tensor:
     """Tree-attention decode of q (b, h, nq, d) over k, v (b, hk, n, dv).
+
+    `softclamp_qk_sim` / `softclamp_value` are ring_flash_attn's (Gemma-2
+    style logit capping): sim = c * tanh(q.k * d**-0.5 / c), c =
+    softclamp_value > 0 (ValueError otherwise), applied before any mask, so a
+    model trained with the clamp decodes with the function it was trained on.
+    Every serving entry point of this module and of paged_prefill takes the
+    pair with this meaning.
 
     `tree_mask` / `causal` verify drafts on the dense cache with
     tree_attn_decode_paged's meaning (minus the window): the last nq keys of
@@ -151,6 +178,7 @@ def tree_attn_decode(
     dtype = q.dtype
     b, h, nq, d = q.shape
     name = "tree_attn_decode"
+    _check_softclamp(name, softclamp_qk_sim, softclamp_value)
 
     # capture the value dim from the FULL v before chunking: a rank whose
     # shard is empty must still pack a (b,h,1,1+dv)-shaped all-reduce buffer,
@@ -172,7 +200,8 @@ def tree_attn_decode(
         None if k is None else k.shape[-2], q.device, masked_here)
 
     if v is not None:
-        local_out, lse = _local_decode_partial(q, k, v, use_hip_kernel, vis, use_grouped)
+        local_out, lse = _local_decode_partial(q, k, v, use_hip_kernel, vis, use_grouped,
+                                               softclamp_qk_sim, softclamp_value)
     else:
         # seq shorter than world: this rank holds nothing
         local_out = q.new_zeros((b, h, nq, dim_v), dtype=torch.float32)
@@ -208,6 +237,8 @@ def tree_attn_decode_fp8(
     causal: bool = False,
     tree_mask: Tensor | None = None,
     grouped: bool | None = None,
+    softclamp_qk_sim: bool = False,
+    softclamp_value: float = 50.0,
 ) -> Tensor:
     """Tree-attention decode over an FP8-quantized LOCAL KV-cache shard.
 
@@ -220,10 +251,14 @@ def tree_attn_decode_fp8(
 
     `causal`, `tree_mask` and `grouped` are tree_attn_decode's: the last nq
     keys of the shard are the drafts' own tokens, so only the rank that holds
-    the tail of the sequence passes a mask.
+    the tail of the sequence passes a mask.  `softclamp_qk_sim` /
+    `softclamp_value` are tree_attn_decode's; the clamp applies to the true
+    score, after the e8m0 key scale.
     """
     dtype = q.dtype
     b, _, nq, d = q.shape
+    _check_softclamp("tree_attn_decode_fp8", softclamp_qk_sim, softclamp_value)
+    clamp = (bool(softclamp_qk_sim), float(softclamp_value))
     use_grouped, vis = _dense_visibility("tree_attn_decode_fp8", tree_mask, grouped,
                                          causal, b, nq, k8.shape[-2], q.device)
     if q.is_cuda:
@@ -231,10 +266,10 @@ def tree_attn_decode_fp8(
         if use_grouped:
             outs, lses = hip_ext.require().decode_partial_grouped(
                 q.to(torch.bfloat16).contiguous(), k8, v8, ks, vs, d ** -0.5, 0,
-                None if vis is None else _tree_bits(vis))
+                None if vis is None else _tree_bits(vis), *clamp)
         else:
             outs, lses = hip_ext.require().decode_partial_fp8(
-                q.to(torch.bfloat16).contiguous(), k8, v8, ks, vs, d ** -0.5)
+                q.to(torch.bfloat16).contiguous(), k8, v8, ks, vs, d ** -0.5, 0, *clamp)
         local_out, lse = hip_ext.require().decode_merge(outs, lses)
     else:
         # CPU fallback: dequantize the cache and run the eager partial (the
@@ -244,7 +279,9 @@ def tree_attn_decode_fp8(
               * torch.exp2(ks.float() - 127.0).unsqueeze(-1))
         vd = (v8.view(torch.float8_e4m3fn).float()
               * torch.exp2(vs.float() - 127.0).unsqueeze(-1))
-        local_out, lse = _local_decode_partial(q, kd, vd, vis=vis)
+        local_out, lse = _local_decode_partial(q, kd, vd, vis=vis,
+                                               softclamp_qk_sim=clamp[0],
+                                               softclamp_value=clamp[1])
     return _merge_across_ranks(local_out, lse, dtype, eps)
 
 
@@ -325,7 +362,9 @@ def _local_paged_decode_partial(q: Tensor, cache, causal: bool = False,
                                 use_hip_kernel: bool | None = None,
                                 chunks: int = 0, window: int | None = None,
                                 kv_after=None, tree_mask: Tensor | None = None,
-                                grouped: bool | None = None) -> tuple[Tensor, Tensor]:
+                                grouped: bool | None = None,
+                                softclamp_qk_sim: bool = False,
+                                softclamp_value: float = 50.0) -> tuple[Tensor, Tensor]:
     """Local flash-decode partial over a PagedKVCache:
     (out fp32 (b,h,nq,d), lse fp32 (b,h,nq,1)).
 
@@ -353,8 +392,13 @@ def _local_paged_decode_partial(q: Tensor, cache, causal: bool = False,
     either way; see tree_attn_decode_paged for the rules.  `grouped=True`
     takes `window` / `kv_after` and a released cache with the meaning above
     (the kernel's windowed variant); `tree_mask` takes neither.
+    `softclamp_qk_sim` / `softclamp_value` (tree_attn_decode's) cap the scores
+    before any of these masks, in the row kernel, the grouped kernel and the
+    eager path alike.
     """
     b, h, nq, d = q.shape
+    _check_softclamp("tree_attn_decode_paged", softclamp_qk_sim, softclamp_value)
+    clamp = (bool(softclamp_qk_sim), float(softclamp_value))
     assert b == cache.max_seqs and d == cache.dim_head
     assert h % cache.kv_heads == 0
     use_grouped, vis = _tree_visibility(tree_mask, grouped, causal, window, cache,
@@ -393,14 +437,14 @@ def _local_paged_decode_partial(q: Tensor, cache, causal: bool = False,
                 cache.k_pages, cache.v_pages, cache.k_scales, cache.v_scales,
                 cache.block_table, cache.seq_lens, cache.max_seq_len,
                 d ** -0.5, chunks, None if vis is None else _tree_bits(vis),
-                *win_args)
+                *win_args, *clamp)
             out, lse = ext.decode_merge(outs, lses)
             return (out[..., :d] if d != kd else out), lse
         outs, lses = ext.decode_partial_paged(
             qb.to(torch.bfloat16).contiguous(),
             cache.k_pages, cache.v_pages, cache.k_scales, cache.v_scales,
             cache.block_table, cache.seq_lens, cache.max_seq_len,
-            d ** -0.5, causal, chunks, *win_args)
+            d ** -0.5, causal, chunks, *win_args, *clamp)
         out, lse = ext.decode_merge(outs, lses)
         if d != kd:
             out = out[..., :d]
@@ -422,7 +466,7 @@ def _local_paged_decode_partial(q: Tensor, cache, causal: bool = False,
         kf, vf = cache.gather(i)
         kf = kf.float().repeat(groups, 1, 1)            # tile pairing qh % hk
         vf = vf.float().repeat(groups, 1, 1)
-        sim = torch.einsum("hid,hjd->hij", q[i].float(), kf) * scale
+        sim = _softclamp(torch.einsum("hid,hjd->hij", q[i].float(), kf) * scale, *clamp)
         if vis is not None:                             # prefix open, drafts by mask
             masked = torch.zeros(nq, n, dtype=torch.bool, device=q.device)
             masked[:, n - nq:] = ~vis[i]
@@ -455,6 +499,8 @@ def tree_attn_decode_paged(
     kv_after=None,
     tree_mask: Tensor | None = None,
     grouped: bool | None = None,
+    softclamp_qk_sim: bool = False,
+    softclamp_value: float = 50.0,
 ) -> Tensor:
     """Tree-attention decode over a paged KV cache with per-sequence lengths.
 
@@ -492,8 +538,13 @@ def tree_attn_decode_paged(
     grouped=False, with `window` or with a cache that has released pages
     raises ValueError before anything runs, as does a violated rule above
     (lengths come from the host mirrors).
+
+    `softclamp_qk_sim` / `softclamp_value` are tree_attn_decode's and combine
+    with every legal combination of the arguments above.
     """
     local_out, lse = _local_paged_decode_partial(q, cache, causal, use_hip_kernel,
                                                  window=window, kv_after=kv_after,
-                                                 tree_mask=tree_mask, grouped=grouped)
+                                                 tree_mask=tree_mask, grouped=grouped,
+                                                 softclamp_qk_sim=softclamp_qk_sim,
+                                                 softclamp_value=softclamp_value)
     return _merge_across_ranks(local_out, lse, q.dtype, eps)

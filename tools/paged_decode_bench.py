@@ -33,7 +33,7 @@ shape has that many) and as the launcher picks them; `vs_row` is grouped / row.
 
     python tools/paged_decode_bench.py [--kv-len 131072] [--rounds 7] [--out F]
         [--window 1024 4096 32768] [--only-window] [--grouped 1 4 16]
-        [--dense-grouped 1 4 16]
+        [--dense-grouped 1 4 16] [--softclamp 50]
 """
 
 from __future__ import annotations
@@ -148,6 +148,9 @@ def main():
                     help="query tokens per head: time the grouped kernel on the DENSE "
                          "cache (at most 1, 2, 4 tiles per workgroup and its own pick) "
                          "against the dense row kernel and nothing else")
+    ap.add_argument("--softclamp", type=float, default=None, metavar="VALUE",
+                    help="with --grouped: also time both kernels with "
+                         "softclamp_qk_sim=True at this softclamp_value, in the same rounds")
     ap.add_argument("--out", default=None, help="also write the records here (JSON)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "paged_decode_bench needs a GPU"
@@ -196,6 +199,15 @@ def main():
                              qn, c, window=w, grouped=True)}
                 err = (steps["grouped"]()[0] - steps["row"]()[0]).abs().max().item()
                 assert err < 5e-3, (nq, fp8, w, err)
+                if args.softclamp is not None:
+                    clamp = dict(softclamp_qk_sim=True, softclamp_value=args.softclamp)
+                    steps["row softclamp"] = lambda c=cache, w=w: _local_paged_decode_partial(
+                        qn, c, window=w, **clamp)
+                    steps["grouped softclamp"] = lambda c=cache, w=w: _local_paged_decode_partial(
+                        qn, c, window=w, grouped=True, **clamp)
+                    err = (steps["grouped softclamp"]()[0]
+                           - steps["row softclamp"]()[0]).abs().max().item()
+                    assert err < 5e-3, (nq, fp8, w, "softclamp", err)
                 run_group(f"{'fp8' if fp8 else 'bf16'} b=1 kv={n} {h}q/{hk}kv nq={nq}"
                           + ("" if w is None else f" window={w}"),
                           steps, args, results, base_of=lambda label: "row", ratio="vs_row")

@@ -23,6 +23,7 @@ median over the rounds is reported with min / max; each measurement is
 `--iters` calls between two device events after a warm-up.
 
     python tools/paged_prefill_bench.py [--rounds 5] [--dims 64] [--out F]
+        [--softclamp 50]
 """
 
 from __future__ import annotations
@@ -120,6 +121,9 @@ def main():
     ap.add_argument("--page-sizes", type=int, nargs="+", default=[16, 64, 256])
     ap.add_argument("--dims", type=int, nargs="+", default=[64, 128],
                     help="head dims of the one-sequence shapes (fp8 runs at 64)")
+    ap.add_argument("--softclamp", type=float, default=None, metavar="VALUE",
+                    help="time the 8k full causal prefill (d 64, bf16) with and without "
+                         "softclamp_qk_sim=True at this softclamp_value, and nothing else")
     ap.add_argument("--out", default=None, help="also write the records here (JSON)")
     args = ap.parse_args()
     assert args.rounds >= 5, "report a median of at least 5 rounds"
@@ -163,9 +167,21 @@ def main():
         for label, fn in steps.items():       # same result before anything is timed
             err = (fn().float() - ref).abs().max().item()
             assert err < 2e-2, (label, err)
+        if args.softclamp is not None:        # the same paged steps, clamped
+            clamp = dict(softclamp_qk_sim=True, softclamp_value=args.softclamp)
+            for ps in args.page_sizes:
+                cache = PagedKVCache.from_dense(k, v, [n], ps, fp8=fp8, shuffle_seed=7)
+                steps[f"paged ps={ps} shuffled softclamp"] = (
+                    lambda c=cache: paged_prefill_attn(q, c, [t], causal=True, **clamp))
+                steps[f"varlen ps={ps} shuffled softclamp"] = (
+                    lambda c=cache: paged_prefill_attn_varlen(q[0], c, [t], causal=True,
+                                                              **clamp)[None])
         tag = f"{'fp8' if fp8 else 'bf16'} d={d} T={t} over kv={n}"
         run_group(tag, steps, args, results, note=f"auto kv_split={split}")
 
+    if args.softclamp is not None:
+        one_sequence(8192, 8192, 64, False)
+        return write(args, results)
     for d, fp8 in [(d, False) for d in args.dims] + [(64, True)] * (64 in args.dims):
         one_sequence(8192, 8192, d, fp8)        # full causal prefill of one prompt
         one_sequence(2048, 32768, d, fp8)       # a chunk over a cached context
@@ -224,6 +240,10 @@ def main():
               note=f"defaults target={default[0]} min_tiles={default[1]}",
               base=f"target={default[0]} min_tiles={default[1]}")
 
+    write(args, results)
+
+
+def write(args, results):
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
