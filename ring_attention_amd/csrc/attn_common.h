@@ -474,6 +474,56 @@ long grouped_decode_chunks(const GroupedDecodeParams& p, int head_dim);
 void launch_decode_partial_grouped(const GroupedDecodeParams& p, int head_dim, bool fp8,
                                    hipStream_t stream);
 
+// Shared-prefix paged decode (decode_paged_shared.hip): a flat grid over
+// host-built work units.  A unit's rows are those of its member sequences,
+// stacked r = (m * G + g) * nq + iq; a PREFIX unit runs the members of one
+// group over a span of the pages they share, a SUFFIX unit one sequence over
+// a span of [lo, len).  Masks as in PagedGroupedDecodeParams.
+constexpr int PSU_INTS = 12;
+enum PagedSharedUnitField {
+    PSU_KIND = 0,   // PSU_PREFIX or PSU_SUFFIX
+    PSU_HK = 1,     // kv head
+    PSU_TILE0 = 2,  // first 32-row tile of the stacked rows
+    PSU_NTILE = 3,  // tiles of this unit: 1 or 2
+    PSU_JLO = 4,    // key span [j_lo, j_hi); j_lo is a multiple of 128
+    PSU_JHI = 5,
+    PSU_SLOT = 6,   // S index of the partial this unit writes
+    PSU_MEM0 = 7,   // member list: members[mem0 .. mem0 + nmem)
+    PSU_NMEM = 8,   // (a suffix unit has one member)
+    PSU_LO = 9,     // suffix: keys below lo belong to prefix units; prefix: 0
+    PSU_LEN = 10,   // suffix: the sequence's length; prefix: the shared length
+};
+constexpr int PSU_PREFIX = 0, PSU_SUFFIX = 1;
+
+struct PagedSharedDecodeParams {
+    const void* q;          // bf16 (B, HQ, NQ, D)
+    const void* k_pages;    // bf16 or e4m3 bytes (P, HK, PS, D)
+    const void* v_pages;
+    const void* kscale;     // fp8 mode: e8m0 per row (P, HK, PS)
+    const void* vscale;
+    const int* block_table; // int32 (B, max_pages); read only below a unit's j_hi
+    const int* tree_bits;   // int32 (B, NQ, 2) or null
+    const int* units;       // int32 (n_units, PSU_INTS), host-checked
+    const int* members;     // int32: the units' member lists (sequence ids)
+    float* out;             // fp32 (n_slots, B, HQ, NQ, D) partials
+    float* lse;             // fp32 (n_slots, B, HQ, NQ, 1)
+    int b, h, hk, nq;       // h = HQ; q head qh reads kv head qh % hk
+    int page_shift, max_pages, num_pages;
+    int n_units, n_slots;
+    int unit_tiles;         // most tiles any unit holds (picks the instantiation)
+    float scale;
+    // logit capping (FwdParams' fields): sim = c * tanh(score * scale / c)
+    // before any mask; selects the SOFTCLAMP instantiation on the host
+    int softclamp;          // bool
+    float softclamp_value;  // c > 0
+};
+
+// most row tiles a unit may hold at this head dim
+int paged_shared_unit_tiles(int head_dim);
+// fills the partials with (0, MASK_VALUE_F), then runs the units
+void launch_decode_partial_paged_shared(const PagedSharedDecodeParams& p, int head_dim,
+                                        bool fp8, hipStream_t stream);
+
 struct PagedAppendParams {
     const void* k_new;      // bf16 (B, HK, T, D)
     const void* v_new;      // bf16 (B, HK, T, D)

@@ -763,6 +763,107 @@ std::vector<at::Tensor> decode_partial_paged_grouped(
     return {r.out, r.lse};
 }
 
+at::Tensor paged_shared_upload(at::Tensor plan, int64_t n_units, int64_t n_slots,
+                               int64_t B, int64_t H, int64_t HK, int64_t NQ,
+                               int64_t page_size, int64_t max_pages, bool masked,
+                               int64_t head_dim, at::Device device) {
+    // plan: CPU int32, n_units rows of PSU_INTS followed by the member lists.
+    // Every field is checked here, on the host, against the geometry of the
+    // call it is planned for; the kernel trusts the device copy returned.
+    TORCH_CHECK(plan.device().is_cpu() && plan.scalar_type() == at::kInt
+                && plan.is_contiguous() && plan.dim() == 1,
+                "plan must be a contiguous 1-D int32 CPU tensor");
+    TORCH_CHECK(n_units >= 0 && n_units * PSU_INTS <= plan.numel(), "plan too short");
+    TORCH_CHECK(n_units < (int64_t(1) << 31) && n_slots >= 1 && n_slots < (1 << 20),
+                "unit or slot count out of range");
+    TORCH_CHECK(HK > 0 && H % HK == 0 && NQ >= 1 && B >= 1, "bad head / row geometry");
+    const int64_t n_members = plan.numel() - n_units * PSU_INTS;
+    const int* u = plan.data_ptr<int>();
+    const int* members = u + n_units * PSU_INTS;
+    for (int64_t i = 0; i < n_members; ++i)
+        TORCH_CHECK(members[i] >= 0 && members[i] < B, "member ", i, " is no sequence");
+    const int64_t GN = H / HK * NQ;
+    const int cap = paged_shared_unit_tiles((int)head_dim);
+    for (int64_t i = 0; i < n_units; ++i, u += PSU_INTS) {
+        const bool prefix = u[PSU_KIND] == PSU_PREFIX;
+        TORCH_CHECK(prefix || u[PSU_KIND] == PSU_SUFFIX, "unit ", i, ": kind");
+        TORCH_CHECK(u[PSU_HK] >= 0 && u[PSU_HK] < HK, "unit ", i, ": kv head");
+        TORCH_CHECK(u[PSU_NMEM] >= 1 && (prefix || u[PSU_NMEM] == 1) && u[PSU_MEM0] >= 0
+                    && (int64_t)u[PSU_MEM0] + u[PSU_NMEM] <= n_members,
+                    "unit ", i, ": member list");
+        TORCH_CHECK(u[PSU_NTILE] >= 1 && u[PSU_NTILE] <= cap && u[PSU_TILE0] >= 0
+                    && ((int64_t)u[PSU_TILE0] + u[PSU_NTILE] - 1) * 32 < u[PSU_NMEM] * GN,
+                    "unit ", i, ": row tiles");
+        TORCH_CHECK(u[PSU_JLO] >= 0 && u[PSU_JLO] % 128 == 0 && u[PSU_JLO] <= u[PSU_JHI]
+                    && u[PSU_JHI] <= u[PSU_LEN] && u[PSU_LEN] <= max_pages * page_size,
+                    "unit ", i, ": key span");
+        TORCH_CHECK(u[PSU_LO] >= 0 && u[PSU_LO] < u[PSU_JLO] + 128
+                    && (prefix ? u[PSU_LO] == 0
+                               : u[PSU_LO] <= u[PSU_LEN] - (masked ? NQ : 0)),
+                    "unit ", i, ": lower bound");
+        TORCH_CHECK(u[PSU_SLOT] >= 0 && u[PSU_SLOT] < n_slots, "unit ", i, ": slot");
+    }
+    return plan.to(device);
+}
+
+std::vector<at::Tensor> decode_partial_paged_shared(
+    at::Tensor q, at::Tensor k_pages, at::Tensor v_pages,
+    std::optional<at::Tensor> k_scales, std::optional<at::Tensor> v_scales,
+    at::Tensor block_table, at::Tensor seq_lens, at::Tensor plan, int64_t n_units,
+    int64_t n_slots, int64_t unit_tiles, double sm_scale,
+    std::optional<at::Tensor> tree_bits, bool softclamp, double softclamp_value) {
+    // operands as decode_partial_paged_grouped; `plan` is what
+    // paged_shared_upload returned for this geometry.  Output: the partials
+    // (n_slots, B, HQ, NQ, D) / (n_slots, B, HQ, NQ, 1) of decode_merge.
+    CHECK_BF16_CONTIG(q);
+    TORCH_CHECK(q.dim() == 4, "q must be (B,HQ,NQ,D)");
+    const int64_t B = q.size(0), H = q.size(1), NQ = q.size(2), D = q.size(3);
+    bool fp8 = false;
+    const int shift = check_paged_pool(q, k_pages, v_pages, k_scales, v_scales,
+                                       block_table, seq_lens, B, D, &fp8);
+    const int64_t HK = k_pages.size(1);
+    TORCH_CHECK(H % HK == 0, "q heads must be a multiple of kv heads");
+    TORCH_CHECK(plan.scalar_type() == at::kInt && plan.is_contiguous() && plan.dim() == 1
+                && plan.device() == q.device() && n_units >= 0
+                && n_units * PSU_INTS <= plan.numel(),
+                "plan must be the int32 tensor of paged_shared_upload on q's device");
+    TORCH_CHECK(unit_tiles >= 1 && unit_tiles <= paged_shared_unit_tiles((int)D),
+                "unit_tiles out of range");
+    TORCH_CHECK(n_slots >= 1 && n_slots * B * H * NQ * D < (int64_t(1) << 40),
+                "partials too large");
+    if (tree_bits.has_value()) {
+        TORCH_CHECK(NQ <= 64, "a tree mask covers at most 64 drafts");
+        TORCH_CHECK(tree_bits->scalar_type() == at::kInt && tree_bits->is_contiguous()
+                    && tree_bits->dim() == 3 && tree_bits->size(0) == B
+                    && tree_bits->size(1) == NQ && tree_bits->size(2) == 2
+                    && tree_bits->device() == q.device(),
+                    "tree_bits must be contiguous int32 (B,NQ,2) on q's device");
+    }
+    auto out = at::empty({n_slots, B, H, NQ, D}, q.options().dtype(at::kFloat));
+    auto lse = at::empty({n_slots, B, H, NQ, 1}, q.options().dtype(at::kFloat));
+    if (B * H * NQ == 0) return {out, lse};
+    PagedSharedDecodeParams p{};
+    p.q = q.data_ptr();
+    p.k_pages = k_pages.data_ptr(); p.v_pages = v_pages.data_ptr();
+    if (fp8) { p.kscale = k_scales->data_ptr(); p.vscale = v_scales->data_ptr(); }
+    p.block_table = block_table.data_ptr<int>();
+    p.tree_bits = tree_bits.has_value() ? tree_bits->data_ptr<int>() : nullptr;
+    p.units = plan.data_ptr<int>();
+    p.members = p.units + n_units * PSU_INTS;
+    p.out = out.data_ptr<float>(); p.lse = lse.data_ptr<float>();
+    p.b = (int)B; p.h = (int)H; p.hk = (int)HK; p.nq = (int)NQ;
+    p.page_shift = shift;
+    p.max_pages = (int)block_table.size(1);
+    p.num_pages = (int)k_pages.size(0);
+    p.n_units = (int)n_units; p.n_slots = (int)n_slots;
+    p.unit_tiles = (int)unit_tiles;
+    p.scale = sm_scale > 0 ? (float)sm_scale : (float)(1.0 / std::sqrt((double)D));
+    SET_SOFTCLAMP(p, softclamp, softclamp_value);
+    launch_decode_partial_paged_shared(p, (int)D, fp8, at::hip::getCurrentHIPStream());
+    TORCH_CHECK(hipGetLastError() == hipSuccess, "shared-prefix paged decode launch failed");
+    return {out, lse};
+}
+
 std::vector<at::Tensor> decode_partial_grouped(
     at::Tensor q, at::Tensor k, at::Tensor v,
     std::optional<at::Tensor> kscale, std::optional<at::Tensor> vscale,
@@ -1135,6 +1236,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::arg("q"), py::arg("k"), py::arg("v"),
             py::arg("kscale") = py::none(), py::arg("vscale") = py::none(),
             py::arg("sm_scale") = -1.0, py::arg("chunks") = 0,
+            py::arg("tree_bits") = py::none(), py::arg("softclamp") = false,
+            py::arg("softclamp_value") = 50.0);
+    mod.def("paged_shared_unit_tiles", &ring_attn::paged_shared_unit_tiles,
+            "most row tiles a shared-prefix decode unit may hold", py::arg("head_dim"));
+    mod.def("paged_shared_upload", &ring_attn::paged_shared_upload,
+            "check a shared-prefix decode plan on the host and copy it to the device",
+            py::arg("plan"), py::arg("n_units"), py::arg("n_slots"), py::arg("b"),
+            py::arg("h"), py::arg("hk"), py::arg("nq"), py::arg("page_size"),
+            py::arg("max_pages"), py::arg("masked"), py::arg("head_dim"), py::arg("device"));
+    mod.def("decode_partial_paged_shared", &ring_attn::decode_partial_paged_shared,
+            "CDNA4 shared-prefix paged decode partial over host-built work units",
+            py::arg("q"), py::arg("k_pages"), py::arg("v_pages"),
+            py::arg("k_scales"), py::arg("v_scales"), py::arg("block_table"),
+            py::arg("seq_lens"), py::arg("plan"), py::arg("n_units"), py::arg("n_slots"),
+            py::arg("unit_tiles"), py::arg("sm_scale") = -1.0,
             py::arg("tree_bits") = py::none(), py::arg("softclamp") = false,
             py::arg("softclamp_value") = 50.0);
     mod.def("paged_kv_append", &ring_attn::paged_kv_append,

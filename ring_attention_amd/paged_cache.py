@@ -29,6 +29,13 @@ released slot holds -1, `append` continues at seq_len, and
 that would reuse the released slots is out of scope).  `host_starts[s]` is the
 number of released tokens; the attention entry points refuse, on the host and
 before any launch, a call that would attend below it.
+
+Prefix sharing: `share_prefix(src, dst, tokens)` lets an empty sequence take
+the first whole pages of another by reference (one system prompt behind a
+batch, n samples of one prompt, beams).  Pages carry a host-side reference
+count and go back to the free list when the last holder lets go;
+`prefix_groups()` names the sequences that start with the same pages, for
+`tree_attn_decode_paged(..., shared_prefix=True)`.
 """
 
 from __future__ import annotations
@@ -87,6 +94,10 @@ class PagedKVCache:
         self._pages: list[list[int]] = [[] for _ in range(self.max_seqs)]
         self._lens: list[int] = [0] * self.max_seqs
         self._starts: list[int] = [0] * self.max_seqs
+        # reference counts of the pages more than one sequence holds
+        # (share_prefix); a held page that is not listed has one holder
+        self._refs: dict[int, int] = {}
+        self._version = 0       # bumped by every mutation (keys cached plans)
 
     # ---- host-side views ------------------------------------------------
     @property
@@ -111,9 +122,39 @@ class PagedKVCache:
         return list(self._pages[seq])
 
     def pages_held(self, seq: int | None = None) -> int:
-        """Pages currently owned by `seq` (default: by all sequences)."""
-        rows = self._pages if seq is None else [self._pages[seq]]
-        return sum(pg >= 0 for row in rows for pg in row)
+        """Pages `seq` references, shared ones included (default: the distinct
+        pages held by all sequences, a shared page counting once)."""
+        if seq is not None:
+            return sum(pg >= 0 for pg in self._pages[seq])
+        return len({pg for row in self._pages for pg in row if pg >= 0})
+
+    def prefix_groups(self) -> list[tuple[list[int], int]]:
+        """[(seqs, tokens), ...]: the sequences that start with the same pages
+        and how many tokens they share, from the host mirrors alone.
+
+        Sequences are grouped by the page id in table slot 0 (an empty
+        sequence, or one whose slot 0 is released, is in no group); a group's
+        length is page_size times the longest run of leading slots whose ids
+        agree across ALL its members.  Groups of one are left out.  Sharing
+        is one level only: after nested forks (A -> B at 64, B -> C at 32)
+        the three form one group at the run common to all of them (32), and
+        what A and B share beyond it is read per sequence.
+        """
+        by_first: dict[int, list[int]] = {}
+        for s, row in enumerate(self._pages):
+            if self._lens[s] > 0 and row and row[0] >= 0:
+                by_first.setdefault(row[0], []).append(s)
+        groups = []
+        for seqs in by_first.values():
+            if len(seqs) < 2:
+                continue
+            first = self._pages[seqs[0]]
+            run = min(len(self._pages[s]) for s in seqs)
+            for s in seqs[1:]:
+                row = self._pages[s]
+                run = next((i for i in range(run) if row[i] != first[i]), run)
+            groups.append((seqs, run * self.page_size))
+        return groups
 
     # ---- construction helpers -------------------------------------------
     @classmethod
@@ -147,6 +188,7 @@ class PagedKVCache:
         assert all(0 <= pg < num_pages for pg in used), "invalid page id in a valid slot"
         assert len(used) == sum(len(r) for r in self._pages), "page referenced twice"
         self._free = [pg for pg in range(num_pages - 1, -1, -1) if pg not in used]
+        self._refs, self._version = {}, 0
         return self
 
     @classmethod
@@ -222,6 +264,63 @@ class PagedKVCache:
             self.seq_lens += append_lens
             for s in range(b):
                 self._lens[s] += lens[s]
+        self._version += 1
+
+    def share_prefix(self, src: int, dst: int, tokens: int) -> None:
+        """Sequence `dst` takes the first `tokens` tokens of `src` by
+        reference: its table slots [0, tokens / page_size) receive src's page
+        ids (one index_copy_), its length becomes `tokens`, and every such
+        page gains a holder.  Nothing is read from the device and no K/V row
+        is copied.
+
+        `dst` must be empty (length 0, no pages), `tokens` a positive multiple
+        of page_size with tokens <= host_lens[src], tokens / page_size <=
+        max_pages_per_seq, and `src` must not have released pages; anything
+        else raises ValueError before anything is touched.
+
+        There is no copy-on-write, and none is needed: only WHOLE pages below
+        `tokens` are shared, and `append` writes only at positions >= seq_len
+        >= tokens, so a shared page is never written again and dst's (or
+        src's) next append opens or continues a page of its own.  `free` and
+        `release_prefix` return a shared page to the pool only when its last
+        holder lets go.
+        """
+        ps = self.page_size
+        if not (0 <= src < self.max_seqs and 0 <= dst < self.max_seqs):
+            raise ValueError(f"share_prefix: sequences {src}, {dst} out of range")
+        if self._lens[dst] != 0 or self._pages[dst]:
+            raise ValueError(f"share_prefix: destination {dst} is not empty")
+        if tokens <= 0 or tokens % ps != 0:
+            raise ValueError(f"share_prefix: tokens = {tokens} must be a positive "
+                             f"multiple of page_size = {ps}")
+        if tokens > self._lens[src]:
+            raise ValueError(f"share_prefix: sequence {src} holds {self._lens[src]} "
+                             f"tokens, {tokens} asked for")
+        if self._starts[src] != 0:
+            raise ValueError(f"share_prefix: sequence {src} has released pages")
+        if tokens // ps > self.max_pages_per_seq:
+            raise ValueError(f"share_prefix: {tokens // ps} pages, table rows hold "
+                             f"{self.max_pages_per_seq}")
+        ids = self._pages[src][:tokens // ps]
+        for pg in ids:
+            self._refs[pg] = self._refs.get(pg, 1) + 1
+        self._pages[dst] = list(ids)
+        self._lens[dst] = tokens
+        self.block_table.view(-1).index_copy_(
+            0, (torch.arange(len(ids)) + dst * self.max_pages_per_seq).to(self.device),
+            torch.tensor(ids, dtype=torch.int32).to(self.device))
+        self.seq_lens[dst].fill_(tokens)
+        self._version += 1
+
+    def _drop(self, pg: int) -> None:
+        """One holder lets go of page `pg`: free it if that was the last."""
+        n = self._refs.get(pg, 1) - 1
+        if n == 0:
+            self._free.append(pg)
+        elif n == 1:
+            del self._refs[pg]
+        else:
+            self._refs[pg] = n
 
     def _pad(self, x: Tensor) -> Tensor:
         d = x.shape[-1]
@@ -293,10 +392,11 @@ class PagedKVCache:
         for s in range(self.max_seqs):
             start = min(keep[s], self._lens[s]) // ps * ps
             for slot in range(self._starts[s] // ps, start // ps):
-                self._free.append(self._pages[s][slot])
+                self._drop(self._pages[s][slot])
                 self._pages[s][slot] = -1
                 flat_idx.append(s * self.max_pages_per_seq + slot)
             self._starts[s] = max(self._starts[s], start)
+        self._version += 1
         if flat_idx:
             self.block_table.view(-1).index_copy_(
                 0, torch.tensor(flat_idx, dtype=torch.long).to(self.device),
@@ -322,9 +422,13 @@ class PagedKVCache:
                     f"keys below {start} are released (release_prefix)")
 
     def free(self, seq: int) -> None:
-        """Return the pages sequence `seq` still holds to the pool and zero
-        its length and its released prefix."""
-        self._free.extend(pg for pg in reversed(self._pages[seq]) if pg >= 0)
+        """Let go of the pages sequence `seq` still holds (a page shared with
+        another sequence stays out of the pool until its last holder frees it)
+        and zero its length and its released prefix."""
+        for pg in reversed(self._pages[seq]):
+            if pg >= 0:
+                self._drop(pg)
+        self._version += 1
         self._pages[seq] = []
         self._lens[seq] = 0
         self._starts[seq] = 0

@@ -358,13 +358,112 @@ def _tree_bits(vis: Tensor) -> Tensor:
     return torch.where(words >= 1 << 31, words - (1 << 32), words).to(torch.int32).contiguous()
 
 
+_PSU_INTS = 12                  # csrc/attn_common.h PSU_INTS
+_PSU_PREFIX, _PSU_SUFFIX = 0, 1
+_SHARED_TARGET_UNITS = 2 * 256  # planner: workgroups aimed at (two per CU)
+_SHARED_PASS = 128              # keys a workgroup consumes per pass
+
+
+def plan_shared_units(lens, groups, hk: int, rows: int, nq: int, masked: bool,
+                      chunks: int = 0, unit_tiles: int = 2,
+                      target_units: int | None = None):
+    """Work units of one shared-prefix decode call, on the host (nothing is
+    read back): `lens` and `groups` are the cache's `host_lens` and
+    `prefix_groups()`, `rows` = G * nq rows per (sequence, kv head).
+
+    A group's members join its PREFIX span [0, P) when no draft of theirs lies
+    inside it: always without a mask, with one only if P <= len - nq (the
+    others are served whole by their suffix span, as is every sequence outside
+    a group).  Groups left with fewer than two members are dropped.  Every
+    sequence with keys beyond its prefix gets a SUFFIX span [P_s, len), cut
+    from P_s & ~127.  A span's stacked rows make ceil(members * rows / 32)
+    tiles, `unit_tiles` of them per unit; its keys are cut into shares of
+    `per` keys, a multiple of 128: one figure for the whole call, sized so
+    that about `target_units` units result, or with `chunks` > 0
+    ceil(keys / chunks) per span.  Share z of a prefix span writes partial
+    slot z, share z of a suffix span slot S_prefix + z.
+
+    Returns (units, members, n_slots): int rows [kind, kv head, first tile,
+    tiles, j_lo, j_hi, slot, member offset, member count, lo, len, 0],
+    heaviest first; the flat member lists; the number of partial slots.
+    """
+    target = _SHARED_TARGET_UNITS if target_units is None else int(target_units)
+    prefix_of = [0] * len(lens)
+    spans = []                                  # (kind, members, lo, hi)
+    for seqs, shared in groups:
+        joined = [s for s in seqs if not masked or shared <= lens[s] - nq]
+        if len(joined) >= 2 and shared > 0:
+            for s in joined:
+                prefix_of[s] = shared
+            spans.append((_PSU_PREFIX, joined, 0, shared))
+    n_prefix = len(spans)
+    spans += [(_PSU_SUFFIX, [s], prefix_of[s], n) for s, n in enumerate(lens)
+              if n > prefix_of[s]]
+
+    def up(x):                                  # next multiple of a pass
+        return -(-x // _SHARED_PASS) * _SHARED_PASS
+
+    geom = []                                   # (base, keys, tiles) per span
+    for _, mem, lo, hi in spans:
+        base = lo // _SHARED_PASS * _SHARED_PASS
+        geom.append((base, hi - base, -(-len(mem) * rows // 32)))
+    work = sum(keys * -(-tiles // unit_tiles) * hk for _, keys, tiles in geom)
+    per_all = max(_SHARED_PASS, up(-(-work // max(1, target))))
+    counts = []
+    for _, keys, _ in geom:
+        per = up(-(-keys // chunks)) if chunks > 0 else per_all
+        counts.append((per, -(-keys // per)))
+    s_prefix = max((c for _, c in counts[:n_prefix]), default=0)
+    n_slots = max(1, s_prefix + max((c for _, c in counts[n_prefix:]), default=0))
+
+    keyed, members = [], []
+    for (kind, mem, lo, hi), (base, _, tiles), (per, count) in zip(spans, geom, counts):
+        mem0 = len(members)
+        members.extend(mem)
+        for z in range(count):
+            j_lo, j_hi = base + z * per, min(hi, base + (z + 1) * per)
+            slot = z if kind == _PSU_PREFIX else s_prefix + z
+            for tile0 in range(0, tiles, unit_tiles):
+                ntile = min(unit_tiles, tiles - tile0)
+                for head in range(hk):
+                    keyed.append(((j_hi - max(j_lo, lo)) * ntile,
+                                  [kind, head, tile0, ntile, j_lo, j_hi, slot, mem0,
+                                   len(mem), lo, hi, 0]))
+    keyed.sort(key=lambda u: -u[0])             # stable: heaviest first
+    return [u for _, u in keyed], members, n_slots
+
+
+def _shared_plan(ext, cache, h: int, nq: int, masked: bool, chunks: int, device):
+    """The device copy of `plan_shared_units` for this cache state and call
+    shape: (plan tensor, units, slots, most tiles in a unit).  Kept on the
+    cache until it changes (every mutation bumps its version), so repeated
+    steps over an unchanged cache neither plan nor upload again."""
+    plans = cache.__dict__.setdefault("_shared_plans", {})
+    key = (h, nq, masked, chunks, str(device))
+    hit = plans.get(key)
+    if hit is not None and hit[0] == cache._version:
+        return hit[1]
+    hk, kd = cache.kv_heads, cache.kernel_dim
+    units, members, n_slots = plan_shared_units(
+        cache.host_lens, cache.prefix_groups(), hk, h // hk * nq, nq, masked,
+        chunks, ext.paged_shared_unit_tiles(kd))
+    flat = torch.tensor([x for u in units for x in u] + members, dtype=torch.int32)
+    dev = ext.paged_shared_upload(flat, len(units), n_slots, cache.max_seqs, h, hk, nq,
+                                  cache.page_size, cache.max_pages_per_seq, masked, kd,
+                                  device)
+    plan = (dev, len(units), n_slots, max((u[3] for u in units), default=1))
+    plans[key] = (cache._version, plan)
+    return plan
+
+
 def _local_paged_decode_partial(q: Tensor, cache, causal: bool = False,
                                 use_hip_kernel: bool | None = None,
                                 chunks: int = 0, window: int | None = None,
                                 kv_after=None, tree_mask: Tensor | None = None,
                                 grouped: bool | None = None,
                                 softclamp_qk_sim: bool = False,
-                                softclamp_value: float = 50.0) -> tuple[Tensor, Tensor]:
+                                softclamp_value: float = 50.0,
+                                shared_prefix: bool | None = None) -> tuple[Tensor, Tensor]:
     """Local flash-decode partial over a PagedKVCache:
     (out fp32 (b,h,nq,d), lse fp32 (b,h,nq,1)).
 
@@ -395,12 +494,30 @@ def _local_paged_decode_partial(q: Tensor, cache, causal: bool = False,
     `softclamp_qk_sim` / `softclamp_value` (tree_attn_decode's) cap the scores
     before any of these masks, in the row kernel, the grouped kernel and the
     eager path alike.
+
+    `shared_prefix=True` takes the work-unit kernel
+    (csrc/decode_paged_shared.hip): the sequences of a `cache.prefix_groups()`
+    group stream the pages they share once per kv head, for the rows of all
+    of them (`plan_shared_units`); `chunks` > 0 then fixes the shares per
+    span.  It implies `grouped`, takes `causal` or `tree_mask` and the
+    softclamp, and refuses `window`, `kv_after`, a cache with released pages
+    and `grouped=False` with ValueError before any launch.  The result is the
+    same attention: on CPU the eager path runs unchanged.
     """
     b, h, nq, d = q.shape
     _check_softclamp("tree_attn_decode_paged", softclamp_qk_sim, softclamp_value)
     clamp = (bool(softclamp_qk_sim), float(softclamp_value))
     assert b == cache.max_seqs and d == cache.dim_head
     assert h % cache.kv_heads == 0
+    if shared_prefix:
+        for given, what in ((window is not None, "a window"),
+                            (kv_after is not None, "kv_after"),
+                            (any(cache.host_starts), "a cache with released pages"),
+                            (grouped is False, "grouped=False")):
+            if given:
+                raise ValueError(f"tree_attn_decode_paged: shared_prefix=True does "
+                                 f"not serve {what}")
+        grouped = True
     use_grouped, vis = _tree_visibility(tree_mask, grouped, causal, window, cache,
                                         b, nq, q.device)
     if window is not None and window < 0:
@@ -431,6 +548,16 @@ def _local_paged_decode_partial(q: Tensor, cache, causal: bool = False,
         win_args = (window is not None, 0 if window is None else int(window),
                     None if window is None or after is None else
                     torch.tensor(after, dtype=torch.int32).to(q.device))
+        if shared_prefix:
+            plan, n_units, n_slots, unit_tiles = _shared_plan(
+                ext, cache, h, nq, vis is not None, int(chunks), q.device)
+            outs, lses = ext.decode_partial_paged_shared(
+                qb.to(torch.bfloat16).contiguous(),
+                cache.k_pages, cache.v_pages, cache.k_scales, cache.v_scales,
+                cache.block_table, cache.seq_lens, plan, n_units, n_slots, unit_tiles,
+                d ** -0.5, None if vis is None else _tree_bits(vis), *clamp)
+            out, lse = ext.decode_merge(outs, lses)
+            return (out[..., :d] if d != kd else out), lse
         if use_grouped:
             outs, lses = ext.decode_partial_paged_grouped(
                 qb.to(torch.bfloat16).contiguous(),
@@ -501,6 +628,7 @@ def tree_attn_decode_paged(
     grouped: bool | None = None,
     softclamp_qk_sim: bool = False,
     softclamp_value: float = 50.0,
+    shared_prefix: bool | None = None,
 ) -> Tensor:
     """Tree-attention decode over a paged KV cache with per-sequence lengths.
 
@@ -541,10 +669,23 @@ def tree_attn_decode_paged(
 
     `softclamp_qk_sim` / `softclamp_value` are tree_attn_decode's and combine
     with every legal combination of the arguments above.
+
+    `shared_prefix=True` serves a cache whose sequences were forked with
+    `PagedKVCache.share_prefix` (one system prompt behind a batch, n samples
+    of a prompt, beams, each with its draft tree): the pages a
+    `cache.prefix_groups()` group shares are streamed once per kv head for
+    the rows of all its members, by the work-unit kernel, instead of once per
+    sequence.  The result is that of the call without it.  It implies
+    `grouped` and combines with plain, `causal=True`, `tree_mask` and the
+    softclamp; with `window`, `kv_after`, a cache that has released pages or
+    `grouped=False` it raises ValueError before anything runs.  With no group
+    in the cache the same kernel runs one span per sequence.  The default
+    (None) runs what runs without the argument.
     """
     local_out, lse = _local_paged_decode_partial(q, cache, causal, use_hip_kernel,
                                                  window=window, kv_after=kv_after,
                                                  tree_mask=tree_mask, grouped=grouped,
                                                  softclamp_qk_sim=softclamp_qk_sim,
-                                                 softclamp_value=softclamp_value)
+                                                 softclamp_value=softclamp_value,
+                                                 shared_prefix=shared_prefix)
     return _merge_across_ranks(local_out, lse, q.dtype, eps)

@@ -31,9 +31,18 @@ take `window=W` over the `--kv-len` cached keys, one group per W.
 most 1, 2 and 4 row tiles per workgroup (RING_ATTN_GROUPED_TILES, as far as the
 shape has that many) and as the launcher picks them; `vs_row` is grouped / row.
 
+`--shared-prefix P --batch B [B ...] --suffix N` builds one forked cache per
+batch size (page size 64, shuffled pages: B sequences behind P shared tokens,
+N of their own each), and times `shared_prefix=True`
+(csrc/decode_paged_shared.hip) against `grouped=True` on that same cache, one
+query token per head, bf16 and fp8, alternating in the same rounds, and
+returns; `vs_grouped` is shared / grouped.  The cache does not change between
+steps, so the unit plan is built and uploaded once.
+
     python tools/paged_decode_bench.py [--kv-len 131072] [--rounds 7] [--out F]
         [--window 1024 4096 32768] [--only-window] [--grouped 1 4 16]
         [--dense-grouped 1 4 16] [--softclamp 50]
+        [--shared-prefix 8192 --batch 8 32 --suffix 256]
 """
 
 from __future__ import annotations
@@ -148,6 +157,14 @@ def main():
                     help="query tokens per head: time the grouped kernel on the DENSE "
                          "cache (at most 1, 2, 4 tiles per workgroup and its own pick) "
                          "against the dense row kernel and nothing else")
+    ap.add_argument("--shared-prefix", type=int, default=0, metavar="P",
+                    help="tokens every sequence of the batch shares (share_prefix): time "
+                         "shared_prefix=True against grouped=True on one forked cache "
+                         "and nothing else")
+    ap.add_argument("--batch", type=int, nargs="+", default=[8],
+                    help="with --shared-prefix: sequences behind the prefix")
+    ap.add_argument("--suffix", type=int, default=256,
+                    help="with --shared-prefix: tokens each sequence holds of its own")
     ap.add_argument("--softclamp", type=float, default=None, metavar="VALUE",
                     help="with --grouped: also time both kernels with "
                          "softclamp_qk_sim=True at this softclamp_value, in the same rounds")
@@ -212,6 +229,37 @@ def main():
                           + ("" if w is None else f" window={w}"),
                           steps, args, results, base_of=lambda label: "row", ratio="vs_row")
     if args.grouped:
+        return write(args, results)
+
+    # ---- forked cache: shared-prefix units vs the grouped kernel ------------
+    for b in args.batch if args.shared_prefix else ():
+        ps, prefix, sfx = 64, args.shared_prefix, args.suffix
+        assert prefix % ps == 0 and prefix > 0 and sfx >= 0
+        qb = torch.randn(b, h, 1, d, device=dev, dtype=bf)
+        for fp8 in (False, True):
+            cache = PagedKVCache(prefix // ps + b * (-(-sfx // ps) + 1), ps, hk, d, b,
+                                 -(-(prefix + sfx) // ps) + 1, fp8=fp8, device=dev)
+            cache._free = torch.randperm(cache.num_pages,
+                                         generator=torch.Generator().manual_seed(7)).tolist()
+            kp = torch.randn(b, hk, max(prefix, sfx), d, device=dev, dtype=bf)
+            vp = torch.randn(b, hk, max(prefix, sfx), d, device=dev, dtype=bf)
+            cache.append(kp, vp, [prefix] + [0] * (b - 1))
+            for dst in range(1, b):
+                cache.share_prefix(0, dst, prefix)
+            cache.append(kp, vp, [sfx] * b)
+            steps = {"grouped": lambda c=cache: _local_paged_decode_partial(
+                         qb, c, grouped=True),
+                     "shared": lambda c=cache: _local_paged_decode_partial(
+                         qb, c, shared_prefix=True)}
+            err = (steps["shared"]()[0] - steps["grouped"]()[0]).abs().max().item()
+            assert err < 5e-3, (b, fp8, err)
+            run_group(f"{'fp8' if fp8 else 'bf16'} b={b} prefix={prefix} suffix={sfx} "
+                      f"{h}q/{hk}kv ps={ps}", steps, args, results,
+                      base_of=lambda label: "grouped", ratio="vs_grouped",
+                      note=f"one forked cache, {cache.pages_held()} distinct pages; the "
+                           "unit plan is reused while the cache is unchanged")
+            del cache, steps
+    if args.shared_prefix:
         return write(args, results)
 
     # ---- dense cache: grouped MFMA kernel vs the dense row kernel -----------
