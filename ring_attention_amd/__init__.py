@@ -19,11 +19,12 @@ from .models import (
     RingTransformer,
     apply_rotary_pos_emb,
 )
-from .paged_cache import PagedKVCache
+from .paged_cache import PagedKVCache, PagedLatentCache
 from .paged_prefill import paged_prefill_attn, paged_prefill_attn_varlen
 from .tree_decode import (
     tree_attn_decode,
     tree_attn_decode_fp8,
+    tree_attn_decode_mla,
     tree_attn_decode_paged,
 )
 from .zigzag import zig_zag_attn, zig_zag_pad_seq, zig_zag_shard
@@ -51,7 +52,9 @@ __all__ = [
     "tree_attn_decode",
     "tree_attn_decode_fp8",
     "tree_attn_decode_paged",
+    "tree_attn_decode_mla",
     "PagedKVCache",
+    "PagedLatentCache",
     "paged_prefill_attn",
     "paged_prefill_attn_varlen",
     "zig_zag_attn",

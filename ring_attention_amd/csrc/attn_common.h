@@ -524,6 +524,44 @@ int paged_shared_unit_tiles(int head_dim);
 void launch_decode_partial_paged_shared(const PagedSharedDecodeParams& p, int head_dim,
                                         bool fp8, hipStream_t stream);
 
+// MLA latent-cache paged decode (decode_paged_latent.hip): ONE pool of
+// (P, 1, PS, 576) bf16 rows, a 512-d latent plus a 64-d rope part.  Every
+// query head reads the whole row as its key and the first 512 columns of the
+// same row as its value.  Rows r = h * NQ + iq of a sequence are stacked into
+// 32-row tiles; `causal` is PagedDecodeParams'.
+struct PagedLatentDecodeParams {
+    const void* q;          // bf16 (B, H, NQ, 576)
+    const void* pages;      // bf16 (P, 1, PS, 576)
+    const int* block_table; // int32 (B, max_pages); entries at or beyond
+                            // ceil(seq_len / PS) are never read
+    const int* seq_lens;    // int32 (B): tokens held per sequence (0 legal)
+    float* out;             // fp32 (S, B, H, NQ, 512) per-chunk partials
+    float* lse;             // fp32 (S, B, H, NQ, 1)
+    int b, h, nq;
+    int page_shift, max_pages, num_pages;
+    int causal;             // query iq sees keys [0, seq_len - (nq-1-iq))
+    int chunk_major;        // 1 = kv chunk is the fast workgroup index
+    float scale;
+    long chunks;            // kv-split S (0 = auto from max_seq_len)
+    long max_seq_len;       // host-known upper bound of seq_lens
+};
+
+// the kv-split S the launcher uses (the binding sizes the partials with it)
+long paged_latent_chunks(const PagedLatentDecodeParams& p);
+void launch_decode_partial_latent(const PagedLatentDecodeParams& p, hipStream_t stream);
+
+struct PagedLatentAppendParams {
+    const void* ckv_new;    // bf16 (B, 1, T, 576)
+    void* pages;            // bf16 (P, 1, PS, 576)
+    const int* block_table; // int32 (B, max_pages)
+    const int* seq_lens;    // int32 (B): lengths BEFORE the append
+    const int* append_lens; // int32 (B): 0 <= append_lens[b] <= T
+    int b, t;
+    int page_shift, max_pages, num_pages;
+};
+
+void launch_paged_latent_append(const PagedLatentAppendParams& p, hipStream_t stream);
+
 struct PagedAppendParams {
     const void* k_new;      // bf16 (B, HK, T, D)
     const void* v_new;      // bf16 (B, HK, T, D)

@@ -561,7 +561,7 @@ std::vector<at::Tensor> decode_merge(at::Tensor outs, at::Tensor lses) {
     CHECK_F32_CONTIG(outs); CHECK_F32_CONTIG(lses);
     const int64_t S = outs.size(0), B = outs.size(1), H = outs.size(2),
                   NQ = outs.size(3), D = outs.size(4);
-    TORCH_CHECK(D == 64 || D == 128, "head dim must be 64 or 128");
+    TORCH_CHECK(D == 64 || D == 128 || D == 512, "head dim must be 64, 128 or 512");
     auto out = at::empty({B, H, NQ, D}, outs.options());
     auto lse = at::empty({B, H, NQ, 1}, outs.options());
     DecodeMergeParams p{};
@@ -962,6 +962,100 @@ void paged_kv_append(
     TORCH_CHECK(hipGetLastError() == hipSuccess, "paged append launch failed");
 }
 
+// shared checks of the latent-pool operands; returns log2(page_size)
+static int check_latent_pool(const at::Tensor& ref, const at::Tensor& pages,
+                             const at::Tensor& block_table, const at::Tensor& seq_lens,
+                             int64_t B) {
+    TORCH_CHECK(pages.scalar_type() == at::kBFloat16 && pages.is_contiguous()
+                && pages.dim() == 4 && pages.size(1) == 1 && pages.size(3) == 576,
+                "latent pages must be contiguous bf16 (num_pages, 1, page_size, 576)");
+    const int64_t PS = pages.size(2);
+    TORCH_CHECK(PS >= 16 && PS <= 256 && (PS & (PS - 1)) == 0,
+                "page_size must be a power of two in [16, 256] (got ", PS, ")");
+    TORCH_CHECK(pages.size(0) < (int64_t(1) << 31), "too many pages");
+    TORCH_CHECK(block_table.scalar_type() == at::kInt && block_table.is_contiguous()
+                && block_table.dim() == 2 && block_table.size(0) == B,
+                "block_table must be contiguous int32 (B, max_pages_per_seq)");
+    TORCH_CHECK(seq_lens.scalar_type() == at::kInt && seq_lens.is_contiguous()
+                && seq_lens.dim() == 1 && seq_lens.size(0) == B,
+                "seq_lens must be contiguous int32 (B,)");
+    TORCH_CHECK(block_table.device() == ref.device() && seq_lens.device() == ref.device()
+                && pages.device() == ref.device(),
+                "pages, block_table and seq_lens must be on the same device as q/ckv_new");
+    TORCH_CHECK(block_table.size(1) * PS < (int64_t(1) << 31), "table too wide");
+    int shift = 0;
+    while ((int64_t(1) << shift) < PS) ++shift;
+    return shift;
+}
+
+std::vector<at::Tensor> decode_partial_latent(
+    at::Tensor q, at::Tensor pages, at::Tensor block_table, at::Tensor seq_lens,
+    int64_t max_seq_len, double sm_scale, bool causal, int64_t chunks_in) {
+    // q bf16 (B,H,NQ,576); pages bf16 (P,1,PS,576): key = the row, value = its
+    // first 512 columns.  max_seq_len is the HOST's upper bound of seq_lens.
+    // Returns fp32 partials (S,B,H,NQ,512) / (S,B,H,NQ,1) for decode_merge.
+    CHECK_BF16_CONTIG(q);
+    TORCH_CHECK(q.dim() == 4 && q.size(3) == 576, "q must be (B,H,NQ,576)");
+    TORCH_CHECK(sm_scale > 0 && std::isfinite(sm_scale), "sm_scale must be positive");
+    const int64_t B = q.size(0), H = q.size(1), NQ = q.size(2);
+    const int shift = check_latent_pool(q, pages, block_table, seq_lens, B);
+    TORCH_CHECK(max_seq_len >= 0 && max_seq_len <= block_table.size(1) * pages.size(2),
+                "max_seq_len exceeds what block_table can address");
+    TORCH_CHECK(chunks_in >= 0 && H * NQ < (int64_t(1) << 24), "bad chunks or row count");
+    PagedLatentDecodeParams p{};
+    p.b = (int)B; p.h = (int)H; p.nq = (int)NQ;
+    p.chunks = chunks_in; p.max_seq_len = max_seq_len;
+    const int64_t rows = B * H * NQ;
+    const int64_t S = rows == 0 ? 1 : paged_latent_chunks(p);
+    const int64_t tiles = (H * NQ + 31) / 32;
+    TORCH_CHECK(S <= 65535, "chunks must fit grid.y");
+    TORCH_CHECK(B * tiles * S < (int64_t(1) << 31), "grid too large");
+    auto out = at::empty({S, B, H, NQ, 512}, q.options().dtype(at::kFloat));
+    auto lse = at::empty({S, B, H, NQ, 1}, q.options().dtype(at::kFloat));
+    if (rows == 0) return {out, lse};
+    p.chunks = S;
+    p.q = q.data_ptr(); p.pages = pages.data_ptr();
+    p.block_table = block_table.data_ptr<int>();
+    p.seq_lens = seq_lens.data_ptr<int>();
+    p.out = out.data_ptr<float>(); p.lse = lse.data_ptr<float>();
+    p.page_shift = shift;
+    p.max_pages = (int)block_table.size(1);
+    p.num_pages = (int)pages.size(0);
+    p.causal = causal ? 1 : 0;
+    p.chunk_major = B > 1 ? 1 : 0;
+    p.scale = (float)sm_scale;
+    launch_decode_partial_latent(p, at::hip::getCurrentHIPStream());
+    TORCH_CHECK(hipGetLastError() == hipSuccess, "latent paged decode launch failed");
+    return {out, lse};
+}
+
+void paged_latent_append(at::Tensor ckv_new, at::Tensor pages, at::Tensor block_table,
+                         at::Tensor seq_lens, at::Tensor append_lens) {
+    // ckv_new bf16 (B,1,T,576): token t < append_lens[b] of sequence b is
+    // written at position seq_lens[b] + t (lengths BEFORE the append).
+    CHECK_BF16_CONTIG(ckv_new);
+    TORCH_CHECK(ckv_new.dim() == 4 && ckv_new.size(1) == 1 && ckv_new.size(3) == 576,
+                "ckv_new must be (B,1,T,576)");
+    const int64_t B = ckv_new.size(0), T = ckv_new.size(2);
+    const int shift = check_latent_pool(ckv_new, pages, block_table, seq_lens, B);
+    TORCH_CHECK(append_lens.scalar_type() == at::kInt && append_lens.is_contiguous()
+                && append_lens.dim() == 1 && append_lens.size(0) == B
+                && append_lens.device() == ckv_new.device(),
+                "append_lens must be contiguous int32 (B,) on the same device");
+    TORCH_CHECK(B * T < (int64_t(1) << 31), "append too large");
+    PagedLatentAppendParams p{};
+    p.ckv_new = ckv_new.data_ptr(); p.pages = pages.data_ptr();
+    p.block_table = block_table.data_ptr<int>();
+    p.seq_lens = seq_lens.data_ptr<int>();
+    p.append_lens = append_lens.data_ptr<int>();
+    p.b = (int)B; p.t = (int)T;
+    p.page_shift = shift;
+    p.max_pages = (int)block_table.size(1);
+    p.num_pages = (int)pages.size(0);
+    launch_paged_latent_append(p, at::hip::getCurrentHIPStream());
+    TORCH_CHECK(hipGetLastError() == hipSuccess, "latent append launch failed");
+}
+
 void attn_fwd_paged(
     at::Tensor q, at::Tensor k_pages, at::Tensor v_pages,
     std::optional<at::Tensor> k_scales, std::optional<at::Tensor> v_scales,
@@ -1258,6 +1352,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             py::arg("k_new"), py::arg("v_new"), py::arg("k_pages"),
             py::arg("v_pages"), py::arg("k_scales"), py::arg("v_scales"),
             py::arg("block_table"), py::arg("seq_lens"), py::arg("append_lens"));
+    mod.def("decode_partial_latent", &ring_attn::decode_partial_latent,
+            "CDNA4 MLA latent-cache paged decode partials (d_qk 576, d_v 512)",
+            py::arg("q"), py::arg("pages"), py::arg("block_table"), py::arg("seq_lens"),
+            py::arg("max_seq_len"), py::arg("sm_scale"), py::arg("causal") = false,
+            py::arg("chunks") = 0);
+    mod.def("paged_latent_append", &ring_attn::paged_latent_append,
+            "write new 576-wide rows into a latent paged cache",
+            py::arg("ckv_new"), py::arg("pages"), py::arg("block_table"),
+            py::arg("seq_lens"), py::arg("append_lens"));
     mod.def("attn_fwd_paged", &ring_attn::attn_fwd_paged,
             "CDNA4 paged prefill attention (bf16 or fp8 pages, per-sequence lengths)",
             py::arg("q"), py::arg("k_pages"), py::arg("v_pages"),

@@ -173,6 +173,8 @@ void launch_decode_merge(const DecodeMergeParams& p, int head_dim, hipStream_t s
         hipLaunchKernelGGL(decode_merge_kernel<64>, grid, block, 0, stream, p);
     } else if (head_dim == 128) {
         hipLaunchKernelGGL(decode_merge_kernel<128>, grid, block, 0, stream, p);
+    } else if (head_dim == 512) {       // the latent decode's value dim
+        hipLaunchKernelGGL(decode_merge_kernel<512>, grid, block, 0, stream, p);
     } else {
         __builtin_trap();
     }

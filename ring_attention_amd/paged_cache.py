@@ -15,7 +15,9 @@ and are never dereferenced.  D is the kernel head dim: 64 or 128; a smaller
 `dim_head` is stored zero-padded to the next of those (exact: padded q/k dims
 add 0 to the score, padded v dims are sliced off) while the softmax scale
 stays `dim_head ** -0.5`.  The value dim equals the key dim on the paged path
-(dv == d).  The fp8 pool is exactly `quantize_kv_cache`'s per-row format.
+(dv == d), except in `PagedLatentCache` at the end of this file, the
+576 / 512 single-pool layout of multi-head latent attention.  The fp8 pool is
+exactly `quantize_kv_cache`'s per-row format.
 
 Page allocation is host-side: a free list plus a host mirror of the lengths
 and the table, so appending and decoding never read anything back from the
@@ -82,6 +84,11 @@ class PagedKVCache:
             self.k_pages = torch.zeros(shape, dtype=torch.bfloat16, device=self.device)
             self.v_pages = torch.zeros(shape, dtype=torch.bfloat16, device=self.device)
             self.k_scales = self.v_scales = None
+        self._init_tables()
+
+    def _init_tables(self) -> None:
+        """Block table, lengths and the host-side allocator of an empty cache
+        (num_pages, max_seqs, max_pages_per_seq and device are set)."""
         self.block_table = torch.full((self.max_seqs, self.max_pages_per_seq), -1,
                                       dtype=torch.int32, device=self.device)
         self.seq_lens = torch.zeros(self.max_seqs, dtype=torch.int32, device=self.device)
@@ -222,6 +229,12 @@ class PagedKVCache:
         b, hk, t, d = k.shape
         assert v.shape == k.shape, "paged path requires dv == d"
         assert b == self.max_seqs and hk == self.kv_heads and d == self.dim_head
+        self._append_rows((k, v), t, lens)
+
+    def _append_rows(self, rows: tuple, t: int, lens) -> None:
+        """`append` behind its shape checks: plan the pages on the host, then
+        hand `rows` (the new-token tensors, T = t each) to the writer."""
+        b = self.max_seqs
         if lens is None:
             lens = [t] * b
         elif isinstance(lens, Tensor):
@@ -258,9 +271,9 @@ class PagedKVCache:
         if any(lens):
             append_lens = torch.tensor(lens, dtype=torch.int32).to(self.device)
             if self.device.type == "cuda":
-                self._append_hip(k, v, append_lens)
+                self._append_hip(*rows, append_lens)
             else:
-                self._append_eager(k, v, lens)
+                self._append_eager(*rows, lens)
             self.seq_lens += append_lens
             for s in range(b):
                 self._lens[s] += lens[s]
@@ -457,3 +470,96 @@ class PagedKVCache:
             return x[:, :n, :self.dim_head].contiguous()
 
         return dense(self.k_pages, self.k_scales), dense(self.v_pages, self.v_scales)
+
+
+class PagedLatentCache(PagedKVCache):
+    """Paged cache of multi-head latent attention (MLA, the DeepSeek-V2/V3
+    layout with the up-projections absorbed into q and the output): ONE bf16
+    row of latent_dim + rope_dim = 576 per token.  All query heads share that
+    row as their key, and its first latent_dim = 512 columns are the value.
+
+        k_pages  (num_pages, 1, page_size, 576)   the only pool
+        v_pages  k_pages[..., :512]                a view, no second pool
+
+    Served by `tree_attn_decode_mla`.  The table, the lengths, the host
+    mirrors and free / share_prefix / release_prefix / prefix_groups are the
+    base class's; only (512, 64) has a kernel, other dims raise ValueError.
+    """
+
+    def __init__(self, num_pages: int, page_size: int, max_seqs: int,
+                 max_pages_per_seq: int, latent_dim: int = 512, rope_dim: int = 64,
+                 device="cpu"):
+        if (latent_dim, rope_dim) != (512, 64):
+            raise ValueError(f"PagedLatentCache: only latent_dim 512 with rope_dim 64 "
+                             f"has a kernel (got {latent_dim}, {rope_dim})")
+        assert 16 <= page_size <= 256 and page_size & (page_size - 1) == 0, \
+            "page_size must be a power of two in [16, 256]"
+        self.num_pages, self.page_size = int(num_pages), int(page_size)
+        self.latent_dim, self.rope_dim = latent_dim, rope_dim
+        self.kv_heads, self.dim_head = 1, latent_dim + rope_dim
+        self.kernel_dim = self.dim_head
+        self.max_seqs, self.max_pages_per_seq = int(max_seqs), int(max_pages_per_seq)
+        self.fp8 = False
+        self.device = torch.device(device)
+        self.k_pages = torch.zeros((self.num_pages, 1, self.page_size, self.dim_head),
+                                   dtype=torch.bfloat16, device=self.device)
+        self.v_pages = self.k_pages[..., :latent_dim]
+        self.k_scales = self.v_scales = None
+        self._init_tables()
+
+    @classmethod
+    def from_pages(cls, *args, **kwargs):
+        raise NotImplementedError("PagedLatentCache: build with from_dense or append")
+
+    @classmethod
+    def from_dense(cls, ckv: Tensor, seq_lens, page_size: int,
+                   shuffle_seed: int | None = None,
+                   spare_pages: int = 0) -> "PagedLatentCache":
+        """Build a cache from dense ckv (b, 1, n, 576) holding seq_lens[i]
+        tokens of sequence i; `shuffle_seed` as in PagedKVCache.from_dense."""
+        b, _, n, _ = ckv.shape
+        lens = [int(x) for x in (seq_lens.tolist() if isinstance(seq_lens, Tensor)
+                                 else seq_lens)]
+        assert len(lens) == b and all(0 <= x <= n for x in lens)
+        per_seq = [-(-x // page_size) for x in lens]
+        cache = cls(sum(per_seq) + spare_pages, page_size, b, max(max(per_seq), 1),
+                    device=ckv.device)
+        if shuffle_seed is not None:
+            gen = torch.Generator().manual_seed(shuffle_seed)
+            cache._free = torch.randperm(cache.num_pages, generator=gen).tolist()
+        if max(lens) > 0:
+            cache.append(ckv[:, :, :max(lens)], lens)
+        return cache
+
+    def append(self, ckv: Tensor, lens=None) -> None:
+        """Append tokens: ckv (max_seqs, 1, T, 576); sequence i takes its first
+        lens[i] tokens.  PagedKVCache.append's semantics: planned on the host,
+        nothing written if the pool or a table row would overflow, no device
+        reads."""
+        b, hk, t, d = ckv.shape
+        assert b == self.max_seqs and hk == 1 and d == self.dim_head
+        self._append_rows((ckv,), t, lens)
+
+    def _append_hip(self, ckv: Tensor, append_lens: Tensor) -> None:
+        from .ops import hip_ext
+        hip_ext.require().paged_latent_append(
+            ckv.to(torch.bfloat16).contiguous(), self.k_pages, self.block_table,
+            self.seq_lens, append_lens)
+
+    def _append_eager(self, ckv: Tensor, lens: list[int]) -> None:
+        ps = self.page_size
+        for s, n_new in enumerate(lens):
+            for t in range(n_new):
+                pos = self._lens[s] + t
+                self.k_pages[self._pages[s][pos // ps], 0, pos % ps] = ckv[s, 0, t]
+
+    def gather(self, seq: int) -> tuple[Tensor, Tensor]:
+        """Dense (k (1, n, 576), v (1, n, 512)) of one sequence, bf16 as
+        stored; rows of released pages come back as zeros."""
+        n = self._lens[seq]
+        pages = torch.tensor([max(pg, 0) for pg in self._pages[seq]],
+                             dtype=torch.long).to(self.device)
+        x = self.k_pages[pages]                               # (np, 1, ps, 576)
+        x[:self._starts[seq] // self.page_size] = 0
+        k = x.permute(1, 0, 2, 3).reshape(1, -1, self.dim_head)[:, :n].contiguous()
+        return k, k[..., :self.latent_dim].contiguous()

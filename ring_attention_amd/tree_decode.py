@@ -689,3 +689,80 @@ def tree_attn_decode_paged(
                                                  softclamp_value=softclamp_value,
                                                  shared_prefix=shared_prefix)
     return _merge_across_ranks(local_out, lse, q.dtype, eps)
+
+
+def _local_mla_decode_partial(q: Tensor, cache, causal: bool = False,
+                              scale: float | None = None,
+                              use_hip_kernel: bool | None = None,
+                              chunks: int = 0) -> tuple[Tensor, Tensor]:
+    """Local flash-decode partial over a PagedLatentCache:
+    (out fp32 (b,h,nq,512), lse fp32 (b,h,nq,1)).
+
+    q (b, h, nq, 576) with b == cache.max_seqs; every head attends the
+    sequence's 576-wide rows as keys and their first 512 columns as values.
+    Row (b, iq) attends keys [0, limit), limit = seq_lens[b], or with `causal`
+    max(0, seq_lens[b] - (nq - 1 - iq)).  A row with limit == 0 returns
+    out == 0 with a finite lse <= -1e30 (`_local_paged_decode_partial`'s
+    convention).  On GPU this is csrc/decode_paged_latent.hip plus the fused
+    chunk merge, with no eager fallback; `chunks` > 0 fixes the kv-split.  A
+    cache with released pages raises ValueError before any launch (there is
+    no window on this path).
+    """
+    b, h, nq, d = q.shape
+    assert b == cache.max_seqs and d == cache.dim_head == 576
+    if any(cache.host_starts):
+        raise ValueError("tree_attn_decode_mla: the cache has released pages "
+                         "(release_prefix), and this path has no window")
+    scale = d ** -0.5 if scale is None else float(scale)
+    if q.is_cuda and use_hip_kernel is not False:
+        from .ops import hip_ext
+        ext = hip_ext.require()       # no eager fallback on GPU
+        outs, lses = ext.decode_partial_latent(
+            q.to(torch.bfloat16).contiguous(), cache.k_pages, cache.block_table,
+            cache.seq_lens, cache.max_seq_len, scale, causal, chunks)
+        return tuple(ext.decode_merge(outs, lses))
+
+    # eager path (CPU): gather each sequence, mask by length and tail
+    neg = -torch.finfo(torch.float32).max
+    out = q.new_zeros((b, h, nq, cache.latent_dim), dtype=torch.float32)
+    lse = torch.full((b, h, nq, 1), neg, device=q.device, dtype=torch.float32)
+    for i, n in enumerate(cache.host_lens):
+        if n == 0:
+            continue
+        kf, vf = cache.gather(i)
+        sim = torch.einsum("hid,jd->hij", q[i].float(), kf[0].float()) * scale
+        if causal:
+            limit = n - (nq - 1 - torch.arange(nq, device=q.device))
+            masked = torch.arange(n, device=q.device)[None, :] >= limit[:, None]
+            sim = sim.masked_fill(masked[None], float("-inf"))
+        row_lse = sim.logsumexp(dim=-1, keepdim=True)   # -inf where limit <= 0
+        live = torch.isfinite(row_lse)
+        attn = torch.nan_to_num(torch.softmax(sim, dim=-1))
+        o = torch.einsum("hij,jd->hid", attn, vf[0].float())
+        out[i] = torch.where(live, o, torch.zeros_like(o))
+        lse[i] = torch.where(live, row_lse, torch.full_like(row_lse, neg))
+    return out, lse
+
+
+@torch.no_grad()
+def tree_attn_decode_mla(
+    q: Tensor,
+    cache,
+    causal: bool = False,
+    scale: float | None = None,
+    eps: float = 1e-8,
+    use_hip_kernel: bool | None = None,
+) -> Tensor:
+    """Tree-attention decode over an MLA latent cache (DeepSeek-V2/V3 style,
+    up-projections absorbed): q (b, h, nq, 576) -> (b, h, nq, 512) in q.dtype.
+
+    `cache` is this rank's PagedLatentCache holding its LOCAL shard of every
+    sequence (ragged, 0 tokens is legal).  `scale` defaults to 576 ** -0.5;
+    MLA models pass the scale of their unabsorbed head dim, with a YaRN
+    factor where they use one.  `causal=True` has tree_attn_decode_paged's
+    meaning: only the rank that holds the tail passes it, the last nq cached
+    tokens are the queries' own, and row iq attends [0, len - (nq - 1 - iq)).
+    Ranks merge exactly like tree_attn_decode_paged.
+    """
+    local_out, lse = _local_mla_decode_partial(q, cache, causal, scale, use_hip_kernel)
+    return _merge_across_ranks(local_out, lse, q.dtype, eps)

@@ -32,6 +32,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "decode_paged_grouped.hip"),
         os.path.join(CSRC, "decode_grouped.hip"),
         os.path.join(CSRC, "decode_paged_shared.hip"),
+        os.path.join(CSRC, "decode_paged_latent.hip"),
         os.path.join(CSRC, "rotary.hip"),
     ],
     extra_compile_args={

@@ -39,7 +39,15 @@ query token per head, bf16 and fp8, alternating in the same rounds, and
 returns; `vs_grouped` is shared / grouped.  The cache does not change between
 steps, so the unit plan is built and uploaded once.
 
+`--latent` times the MLA latent-cache step (csrc/decode_paged_latent.hip plus
+the D = 512 chunk merge) against `gather` + fp32 torch einsums on a
+PagedLatentCache: h = 16 and h = 128 on one sequence of `--kv-len` keys, and
+h = 16 on a batch of 32 x `--kv-len` / 16, alternating in the same rounds, and
+returns; `vs_torch` is hip / torch and `tb_s` the unique cache bytes per
+second of the median.
+
     python tools/paged_decode_bench.py [--kv-len 131072] [--rounds 7] [--out F]
+        [--latent]
         [--window 1024 4096 32768] [--only-window] [--grouped 1 4 16]
         [--dense-grouped 1 4 16] [--softclamp 50]
         [--shared-prefix 8192 --batch 8 32 --suffix 256]
@@ -168,11 +176,16 @@ def main():
     ap.add_argument("--softclamp", type=float, default=None, metavar="VALUE",
                     help="with --grouped: also time both kernels with "
                          "softclamp_qk_sim=True at this softclamp_value, in the same rounds")
+    ap.add_argument("--latent", action="store_true",
+                    help="time the MLA latent-cache step (tree_attn_decode_mla's local "
+                         "partial) against gather + torch einsums and nothing else")
     ap.add_argument("--out", default=None, help="also write the records here (JSON)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "paged_decode_bench needs a GPU"
     hip_ext.require()
     dev, bf = "cuda", torch.bfloat16
+    if args.latent:
+        return latent_groups(args, dev, bf)
     n, h, d = args.kv_len, args.heads, args.d_head
     hk = args.kv_heads or h
     results = []
@@ -339,6 +352,37 @@ def main():
               note=f"dense is PADDED to {n} per sequence; the ragged batch "
                    f"holds {frac:.3f} of those bytes")
 
+    write(args, results)
+
+
+def latent_groups(args, dev, bf):
+    """csrc/decode_paged_latent.hip + decode_merge<512> against the only other
+    way to serve a PagedLatentCache: gather + fp32 torch einsums on the same
+    GPU.  page_size 64, shuffled pages, one query token per head.  `tb_s` is
+    the unique cache bytes (tokens x 1152) over the median step time."""
+    from ring_attention_amd import PagedLatentCache
+    from ring_attention_amd.tree_decode import _local_mla_decode_partial
+    results = []
+    n = args.kv_len
+    for h, b, kv in ((16, 1, n), (128, 1, n), (16, 32, n // 16)):
+        torch.manual_seed(1234 + h + b)
+        ckv = torch.randn(b, 1, kv, 576, device=dev, dtype=bf)
+        q = torch.randn(b, h, 1, 576, device=dev, dtype=bf)
+        cache = PagedLatentCache.from_dense(ckv, [kv] * b, 64, shuffle_seed=7)
+        del ckv
+        steps = {"torch": lambda c=cache, q=q: _local_mla_decode_partial(
+                     q, c, use_hip_kernel=False),
+                 "hip": lambda c=cache, q=q: _local_mla_decode_partial(q, c)}
+        err = (steps["hip"]()[0] - steps["torch"]()[0]).abs().max().item()
+        assert err < 5e-3, (h, b, err)
+        first = len(results)
+        run_group(f"latent bf16 b={b} kv={kv} h={h} nq=1 ps=64 shuffled", steps, args,
+                  results, base_of=lambda label: "torch", ratio="vs_torch")
+        for rec in results[first:]:
+            rec["tb_s"] = round(b * kv * 1152 / rec["median_us"] * 1e-6, 3)
+        print(json.dumps({"tb_s": {r["config"]: r["tb_s"] for r in results[first:]}}),
+              flush=True)
+        del cache, steps
     write(args, results)
 
 
